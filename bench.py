@@ -22,9 +22,15 @@ timed alone on rank 0's GPU, the collective's bytes per rank against the xGMI bo
 the fraction of the gather hidden behind extraction.  `--workload c2` at N > 1 is the
 weak-scaling halo variant (32 frames per GPU, 1-slot point-to-point exchange).
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus `roofline`
-(dominant kernel, live HIP-event timing inside the timed region) and `cpu_baseline`
-(the C restatement in oracle/, timed on a bounded sample on this host, rank 0, N=1).
+Prints ONE JSON line (rank 0) with the driver's contract fields.  A plain run does only
+what that line's headline needs: set up, warm up, time the steps, print.  `--full` adds, for
+the headline workload, `roofline` (dominant kernel, kernel-active spans inside the timed
+region), `stages_ms` (an untimed per-stage HIP-event pass), `steps_detail`, `batches_detail`
+(the same steps again with one batch every step) and `cpu_baseline` (the C restatement in
+oracle/, timed on a bounded sample on this host, rank 0, N=1).
+
+`--dump-outputs DIR` writes what the last timed step computed (its lane's slot table and
+match outputs, rows past each count zeroed) as DIR/<name>.npy, float32, at most 64 MB in all.
 """
 from __future__ import annotations
 
@@ -119,6 +125,38 @@ def emit(out: dict, args) -> None:
     if args.ablation_run:
         out["metric"] = "DIAGNOSTIC ablation run, not a measurement: " + out["metric"]
     print(json.dumps(out), flush=True)
+
+
+DUMP_BUDGET = 64 * 1000 * 1000  # bytes over all the arrays of one --dump-outputs
+
+
+def mask_rows(a, counts) -> np.ndarray:
+    """Copy of a [n, cap, ...] table with the rows at and past each counts[i] zeroed (they are
+    not results: a slot's rows past its count keep whatever an earlier batch left there)."""
+    a = np.array(a)
+    for i, c in enumerate(counts):
+        a[i, max(int(c), 0):] = 0
+    return a
+
+
+def dump_outputs(dirname: str, arrays: dict) -> dict:
+    """--dump-outputs: write each array as DIR/<name>.npy in float32, at most DUMP_BUDGET bytes
+    in all.  The arrays are taken smallest first; one larger than its share of what is left
+    of the budget is written as a fixed sample of its flattened elements (sorted indices drawn
+    by default_rng(0): the same elements in every run).  Returns {name: elements written}."""
+    os.makedirs(dirname, exist_ok=True)
+    left, done = DUMP_BUDGET, {}
+    names = sorted(arrays, key=lambda k: (arrays[k].size, k))
+    for i, name in enumerate(names):
+        a = np.ascontiguousarray(arrays[name], dtype=np.float32)
+        share = left // (len(names) - i) - 128  # the .npy header
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).integers(0, a.size, size=share // 4))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        left -= a.nbytes + 128
+        done[name] = int(a.size)
+    return done
 
 
 def default_workload(world: int) -> str:
@@ -262,11 +300,23 @@ def main():
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=32, help="frames per GPU per step")
+    ap.add_argument("--full", action="store_true",
+                    help="c2 / c5: besides the headline also the per-stage HIP-event pass (stages_ms), the Harris "
+                         "roofline from kernel-active spans, per-step end times, the same-batch comparison pass and "
+                         "the CPU baseline (a plain run sets up, warms up, times the steps and prints)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last of them computed (keypoints, descriptors, "
+                         "counts, matches, confidences, match counts) as DIR/<name>.npy, float32, at most 64 MB in all")
+    ap.add_argument("--settle-steps", type=int, default=None,
+                    help="c2 / c5 without --full: untimed steps before the warm-up that bring the clocks up "
+                         "(default: steps / 2, at least 2 and at most 256; --full's per-stage pass takes their place)")
     ap.add_argument("--cpu-sample", type=int, default=8,
-                    help="frames per host thread in the CPU baseline sample (0 = skip)")
-    ap.add_argument("--no-profile", action="store_true", help="skip the untimed per-stage HIP-event pass (stages_ms)")
+                    help="--full: frames per host thread in the CPU baseline sample (0 = skip)")
+    ap.add_argument("--no-profile", action="store_true",
+                    help="--full: skip the untimed per-stage HIP-event pass (stages_ms)")
     ap.add_argument("--no-spans", action="store_true",
-                    help="no kernel-active spans of the Harris launches in the timed region (no roofline)")
+                    help="no kernel-active spans of the Harris launches in the timed region (no roofline); "
+                         "c2 / c5 take them only with --full")
     ap.add_argument("--workload", choices=["c2", "c3", "c4", "c5"], default=None,
                     help="default: c2 at one GPU, c4 at N > 1.  "
                          "c2 = BASELINE configs[1] (the headline line); c3 = configs[2] (256 frames, all "
@@ -304,6 +354,10 @@ def main():
                     help="c4: after the timed run, re-extract a sample of frames and re-match a sample of this "
                          "rank's pairs with the plain (unchunked) calls and require bit-equal results")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and (args.workload == "c4" or (args.workload is None and args.gpus > 1)):
+        ap.error("--dump-outputs covers the batch workloads (c2, c3, c5), not the sharded c4 job")
 
     abl = ablation_switches_set()
     if abl and not args.ablation_run:
@@ -472,7 +526,7 @@ def main():
     # one batch on the GPU at a time; it names the dominant stage, whose events alone
     # stay on during the timed run.
     stages, dom = {}, None
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         nprof = max(2, args.steps // 2)
         prof_enable(True)
         prof_read()
@@ -502,6 +556,16 @@ def main():
         dom = max((k for k in prof_all if k in work and prof_all[k][1]), key=lambda k: prof_all[k][0])
         prof_enable(False)
         prof_read()
+    elif not args.full:
+        # A plain run has no per-stage pass, whose steps also brought the GPU's clocks up before
+        # the warm-up (W = 5 steps are 4 ms of work: 20 timed steps right after them alone read
+        # 37.2-38.2k img/s against 40.4-40.6k with this pass, interleaved on one GPU).  The same
+        # number of untimed steps, one batch at a time, without the events (at most 256, what the
+        # default 500 steps come to: a longer run's clocks are up long before its last steps).
+        for _ in range(min(256, max(2, args.steps // 2)) if args.settle_steps is None else args.settle_steps):
+            step()
+            pipe.join()
+            torch.cuda.synchronize()
 
     def run_steps(nsteps, step_events=None):
         """nsteps steps of the two-lane pipeline from an idle GPU; with step_events, one
@@ -529,14 +593,14 @@ def main():
     step_ev, host_ms = [], []
     # the roofline's timing: kernel-active spans of every Harris launch inside the timed
     # region itself (one atomic per workgroup; no events around the launches)
-    span_on = not args.no_spans
+    span_on = args.full and not args.no_spans
     if span_on:
         for c in ctxs:
             c.profile_spans(P_OCT["pyramid_level"] * (args.steps + 4))
         torch.cuda.synchronize()
     t0 = time.perf_counter()
     ev0.record()
-    run_steps(args.steps, step_ev)
+    run_steps(args.steps, step_ev if args.full else None)
     t_sub = time.perf_counter() - t0
     ev1.record()
     spin_until(ev1)
@@ -562,9 +626,17 @@ def main():
     # overwrites the lanes' tables
     counts_l = lane_counts()
     nmatch = np.concatenate([ln["mout"][2].cpu().numpy() for ln in pipe.lanes])
+    # --dump-outputs: what the last timed step left in its lane (step i runs on lane i % inflight)
+    # (device copies now, before a later pass reuses the lane; written out after those passes)
+    last = None
+    if args.dump_outputs and rank == 0:
+        ln = pipe.lanes[(args.steps - 1) % pipe.inflight]
+        last = [t.clone() for t in (ln["view"].count, ln["view"].xy, ln["view"].desc,
+                                    ln["mout"][2][:P], ln["mout"][0][:P], ln["mout"][1][:P])]
     # per-step end times inside the timed region (not part of `value`)
     step_end = [ev0.elapsed_time(e) for e in step_ev]
-    step_detail = {"end_ms": [round(x, 4) for x in step_end],
+    step_detail = None if not args.full else {
+                   "end_ms": [round(x, 4) for x in step_end],
                    "first_step_ms": round(step_end[0], 4) if step_end else None,
                    # period between the first and the second-to-last step ends: the last step
                    # ends early (its batch runs alone once the other lane has drained)
@@ -580,7 +652,7 @@ def main():
     # the host-path extraction below idles the GPU (a 20-step pass started on dropped clocks
     # read 10 % slow)
     same_value = None
-    if batches is not None and len(batches) > 1:
+    if args.full and batches is not None and len(batches) > 1:
         same_batch[0] = True
         torch.cuda.synchronize()
         if world > 1:
@@ -658,12 +730,19 @@ def main():
             roof["traffic_note"] = "HBM bytes per launch, rocprofv3 PMC (profiles/pmc_traffic.json)"
 
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_sample > 0 and args.workload == "c2":
+    if args.full and rank == 0 and world == 1 and args.cpu_sample > 0 and args.workload == "c2":
         v, dt, nt, nf = cpu_baseline(args.cpu_sample)
         cpu = {"value": round(v, 4), "unit": "images/sec", "cores": nt, "kind": "port",
                "sample": f"oracle/sfm_oracle.c (scalar C restatement) on {nt} host threads, each extracting "
                          f"{args.cpu_sample} synthetic 1080p frames and matching their consecutive pair "
                          f"({nf} frames, {nt * (args.cpu_sample - 1)} pairs) in {dt:.1f} s"}
+
+    dumped = None
+    if last is not None:
+        cnt, xy, desc, nm, mt, cf = (t.cpu().numpy() for t in last)
+        dumped = dump_outputs(args.dump_outputs, {
+            "count": cnt, "xy": mask_rows(xy, cnt), "desc": mask_rows(desc, cnt),
+            "nmatch": nm, "matches": mask_rows(mt, nm), "conf": mask_rows(cf, nm)})
 
     if rank == 0:
         out = {
@@ -675,6 +754,8 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": round(ms_per_step, 3),
+            "full": bool(args.full),
+            "dumped_outputs": dumped,
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -778,11 +859,17 @@ def run_all_pairs(args, torch, dev):
     elems = int(sum(counts[i] * counts[j] for i, j in pairs_np)) * 128 * args.steps
     ms, n = prof.get("match", (0.0, 0))
     ach = MATCH_FLOP_PER_ELEM * elems / 1e12 / (ms / 1e3) if ms else None
+    dumped = None
+    if args.dump_outputs:  # the job's slot table and every pair's matches (the big ones sampled)
+        dumped = dump_outputs(args.dump_outputs, {
+            "count": counts, "xy": mask_rows(slots.xy.cpu().numpy(), counts),
+            "desc": mask_rows(slots.desc.cpu().numpy(), counts), "nmatch": nm,
+            "matches": mask_rows(out[0].cpu().numpy(), nm), "conf": mask_rows(out[1].cpu().numpy(), nm)})
     emit({
         "metric": "images/sec detect+describe+match, 1080p, all pairs (BASELINE configs[2])",
         "value": round(N * args.steps / elapsed, 3), "unit": "images/sec", "n_gpus": 1,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+        "full": bool(args.full), "dumped_outputs": dumped, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
         "data": "synthetic (deterministic integer-generated textured 1080p frames, device-resident f32)",
         "config": {"workload": f"BASELINE configs[2]: {N}x 1080p, ScaleRotInvSIFT 4-level x2 octave pyramid, "
                                f"k=2500, NNRatio 0.85 over all {P} pairs",

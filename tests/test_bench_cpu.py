@@ -116,6 +116,34 @@ def test_roofline_guard_rejects_more_kernel_time_than_the_step():
     assert bench.roofline_guard(dict(ok, launches=0), 0.812)
 
 
+def test_dump_outputs_float32_budget_and_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: every array as float32 .npy; rows past a count zeroed; an array over its
+    share of the byte budget is written as the same sample of its elements in every run."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+
+    import bench
+    assert bench.DUMP_BUDGET <= 64 * 1000 * 1000
+    t = np.arange(3 * 4 * 2, dtype=np.int32).reshape(3, 4, 2) + 1
+    m = bench.mask_rows(t, [1, -1, 9])
+    assert (m[0, :1] == t[0, :1]).all() and not m[0, 1:].any() and not m[1].any() and (m[2] == t[2]).all()
+    assert t.all()  # the caller's table is left alone
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 4096)
+    big = np.arange(5000, dtype=np.float64) * 0.5
+    arrays = {"count": np.array([3, 0, 7], np.int32), "xy": m, "big": big}
+    for d in ("a", "b"):
+        done = bench.dump_outputs(str(tmp_path / d), arrays)
+        files = sorted(os.listdir(tmp_path / d))
+        assert files == ["big.npy", "count.npy", "xy.npy"]
+        assert sum(os.path.getsize(tmp_path / d / f) for f in files) <= 4096
+        got = {f[:-4]: np.load(tmp_path / d / f) for f in files}
+        assert all(v.dtype == np.float32 for v in got.values())
+        assert np.array_equal(got["count"], [3, 0, 7]) and np.array_equal(got["xy"], m)
+        assert done["big"] == got["big"].size < big.size and got["big"].ndim == 1
+        assert np.isin(got["big"], big.astype(np.float32)).all()
+    assert np.array_equal(np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy"))
+
+
 def test_shipped_library_reads_only_product_switches():
     """Every SFMFEAT_* name in the shipped library is a product switch that
     tests/test_gpu_switches.py runs against the default bit for bit; the diagnostic A/B

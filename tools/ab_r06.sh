@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 O=gpurun_out
 T=${TAG:-r06_ab}
 N=${N:-3}
-ARGS=${ARGS:---steps 200 --cpu-sample 0 --no-profile}
+ARGS=${ARGS:---steps 200 --full --cpu-sample 0 --no-profile}
 BASE=${BASE:-ab/base/libsfmfeat.so}
 run() {  # run NAME ENV... -- ARGS
   local name=$1; shift

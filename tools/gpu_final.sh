@@ -26,7 +26,7 @@ if [ "${SKIP_TESTS:-0}" != 1 ]; then
   tail -1 $O/${T}_smoke.out
 fi
 for i in 1 2 3; do
-  step bench_$i 300 python bench.py --gpus 1 --steps 20 --warmup 5
+  step bench_$i 300 python bench.py --gpus 1 --steps 20 --warmup 5 --full
   python -c "import json;d=json.load(open('$O/${T}_bench_$i.out'));print('c2', d['value'], d['ms_per_step'], d['roofline']['frac'])"
 done
 step bench_c3 300 python bench.py --workload c3 --steps 5 --warmup 2 --cpu-sample 0
@@ -35,7 +35,7 @@ step bench_c5 300 python bench.py --workload c5 --steps 100 --warmup 5 --cpu-sam
 for w in c3 c4 c5; do python -c "import json;d=json.load(open('$O/${T}_bench_$w.out'));print('$w', d['value'], d['ms_per_step'])"; done
 fi
 [ "$PH" = 1 ] && { echo done; exit 0; }
-step trace 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${T}_prof -o run -- python bench.py --steps 20 --warmup 5 --cpu-sample 0 --no-profile
+step trace 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${T}_prof -o run -- python bench.py --steps 20 --warmup 5 --full --cpu-sample 0 --no-profile
 python tools/trace_summary.py $O/${T}_prof > $O/${T}_trace_summary.txt
 for c in FETCH_SIZE WRITE_SIZE; do
   step pmc_$c 300 rocprofv3 --pmc $c --output-format csv -d $O/${T}_pmc_$c -o run -- python bench.py --steps 2 --warmup 1 --cpu-sample 0 --no-profile

@@ -30,11 +30,11 @@ for s in ${STEPS:-tests smoke bench trace}; do
       tail -1 $O/${T}_smoke.out ;;
     bench)
       for i in $(seq 1 ${BENCH_N:-1}); do
-        step bench_$i 300 python bench.py ${BENCH_ARGS:---gpus 1 --steps 20 --warmup 5}
+        step bench_$i 300 python bench.py ${BENCH_ARGS:---gpus 1 --steps 20 --warmup 5 --full}
         python -c "import json;d=json.load(open('$O/${T}_bench_$i.out'));r=d['roofline'];print('c2', d['value'], d['ms_per_step'], r['frac'], r['ms_per_step'], r['launch_sum'])"
       done ;;
     trace)
-      step trace 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${T}_prof -o run -- python bench.py --steps 20 --warmup 5 --cpu-sample 0 --no-profile
+      step trace 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${T}_prof -o run -- python bench.py --steps 20 --warmup 5 --full --cpu-sample 0 --no-profile
       python tools/trace_summary.py $O/${T}_prof > $O/${T}_trace_summary.txt
       python tools/trace_roofline.py $O/${T}_prof --steps 20 --warmup 5 --bench $O/${T}_trace.out > $O/${T}_trace_roofline.json
       cat $O/${T}_trace_roofline.json ;;

@@ -22,7 +22,7 @@ if [ "${SKIP_TESTS:-0}" != 1 ]; then
   tail -15 $OUT/pytest_gpu.log
   step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" || { tail -20 $OUT/smoke.log; exit 1; }
 fi
-step bench 600 python bench.py --steps ${STEPS:-10} --warmup 3 ${BENCH_ARGS:-} || { tail -20 $OUT/bench.log; exit 1; }
+step bench 600 python bench.py --steps ${STEPS:-10} --warmup 3 --full ${BENCH_ARGS:-} || { tail -20 $OUT/bench.log; exit 1; }
 tail -1 $OUT/bench.log
 if [ "${SKIP_PROF:-0}" != 1 ]; then
   step rocprof 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$TAG -o run -- \
