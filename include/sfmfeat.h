@@ -238,7 +238,7 @@ int32_t sfm_match_pairs_dev(sfm_ctx* ctx, const float* desc, const int32_t* coun
  * Matcher workspace (both calls): operands 520 B per slot (x capP = cap rounded up to
  * 128) for the table, plus per pair cap x 532 B (row results, overflow list and 128
  * admitted-target words per query row).  The per-pair part is bounded: a call with more
- * pairs than fit the budget (default 2 GiB, env SFMFEAT_MATCH_BUDGET_MB read at context
+ * pairs than fit the budget (default 4 GiB, env SFMFEAT_MATCH_BUDGET_MB read at context
  * creation) runs as consecutive sub-launches over the same buffers.
  */
 int32_t sfm_match_prep_dev(sfm_ctx* ctx, const float* desc, const int32_t* count, int32_t nimg,
@@ -268,7 +268,9 @@ int32_t sfm_ctx_stream(sfm_ctx* ctx, void** stream);
  * table (desc, count, cap) preps only the slots beyond the extraction's batch — one launch
  * fewer per batch (BatchPipeline turns it on for its own tables).  Contract: the
  * descriptors an extraction wrote are not modified before that match (or
- * sfm_match_prep_dev is called over them first); 0 (default) = off. */
+ * sfm_match_prep_dev is called over them first); 0 (default) = off.  A fused extraction
+ * invalidates earlier sfm_match_prep_dev preps on that context (a prepped match is then
+ * SFM_ESTATE until the table is prepped again). */
 int32_t sfm_ctx_set_fused_prep(sfm_ctx* ctx, int32_t on);
 int32_t sfm_ctx_set_serial(sfm_ctx* ctx, int32_t serial);
 int32_t sfm_ctx_set_priority(sfm_ctx* ctx, int32_t priority);

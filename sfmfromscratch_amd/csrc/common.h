@@ -8,6 +8,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #define SFM_DEV __device__ __forceinline__
 
@@ -28,6 +29,12 @@
 #define SFM_DIAG_ENV(name) SFM_ABLATION_ENV(name)
 
 namespace sfm {
+
+// Host: parse of an environment switch's *value*.  Call sites pass getenv("SFMFEAT_X") (product
+// switch) or SFM_DIAG_ENV / SFM_ABLATION_ENV("SFMFEAT_X") with the literal name, so a name the
+// shipped library does not read is not in it either (tests/test_bench_cpu.py).
+inline int env_int(const char* value, int dflt) { return value ? atoi(value) : dflt; }
+inline bool env_flag(const char* value) { return value && value[0] == '1'; }  // "1..." only
 
 constexpr int kWave = 64;
 

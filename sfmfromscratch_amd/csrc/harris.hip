@@ -817,15 +817,6 @@ void harris_taps_build(const float* g, int ks, float* out) {
     }
 }
 
-static int env_int(const char* name, int dflt) {  // product switch (tests/test_gpu_switches.py)
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
-static int diag_int(const char* name, int dflt) {  // diagnostic build only (SFM_DIAG_ENV)
-  const char* e = SFM_DIAG_ENV(name);
-  return e ? atoi(e) : dflt;
-}
-
 template <int KS, int ABL, int F>
 static void launch_form(HarrisLevels g, int B, const float* gk, float alpha, hipStream_t st) {
   using S = HarrisShape<F>;
@@ -835,10 +826,10 @@ static void launch_form(HarrisLevels g, int B, const float* gk, float alpha, hip
   // -> 34.8-35.5k img/s on the headline (13 per plane: 33.0k, 15: 32.5k, 16: 33.4k, 18:
   // 34.2-34.6k; DESIGN_LOG.md §B); at 8 planes of 4K 448 cost 6 % and 480 (60 per plane)
   // measured best (6.15-6.17k against 5.98-6.00k img/s at 512, 5.95k at 576, 5.87k at 640).
-  static const int slots_env = env_int("SFMFEAT_HARRIS_SLOTS", 0);
+  static const int slots_env = env_int(getenv("SFMFEAT_HARRIS_SLOTS"), 0);
   // SFMFEAT_HARRIS_SLOTS_UPPER=n (A/B): the budget of levels above the first (fewer than
   // 200 64 x 64 tiles per plane)
-  static const int slots_up = diag_int("SFMFEAT_HARRIS_SLOTS_UPPER", 0);
+  static const int slots_up = env_int(SFM_DIAG_ENV("SFMFEAT_HARRIS_SLOTS_UPPER"), 0);
   int slots2 = slots_env > 0 ? slots_env : (B >= 16 ? 448 : 480);
   if (slots_up > 0 && g.n == 1 && ((g.l[0].W + kHT - 1) / kHT) * ((g.l[0].H + kHT - 1) / kHT) < 200) slots2 = slots_up;
   bool vec = true;
@@ -857,22 +848,22 @@ static void launch_form(HarrisLevels g, int B, const float* gk, float alpha, hip
 template <int KS, int ABL = 0>
 static void launch_ks(HarrisLevels g, int B, const float* gk, float alpha, hipStream_t st) {
   // SFMFEAT_HARRIS_PRIO=1: tile-balancing issue priority (A/B)
-  static const int prio = diag_int("SFMFEAT_HARRIS_PRIO", 0);
+  static const int prio = env_int(SFM_DIAG_ENV("SFMFEAT_HARRIS_PRIO"), 0);
   // SFMFEAT_HARRIS_NPAIR=1: the four-wave form for every level (A/B)
-  static const int npair = diag_int("SFMFEAT_HARRIS_NPAIR", 2);
+  static const int npair = env_int(SFM_DIAG_ENV("SFMFEAT_HARRIS_NPAIR"), 2);
   // SFMFEAT_HARRIS_SMALL=t: levels whose 64 x 64 tiles number at most t per resident
   // workgroup (over the batch) take the 64 x 32 form (0: never)
-  static const int small = diag_int("SFMFEAT_HARRIS_SMALL", kHarrisSmallTiles);
+  static const int small = env_int(SFM_DIAG_ENV("SFMFEAT_HARRIS_SMALL"), kHarrisSmallTiles);
   g.prio = prio;
   // SFMFEAT_HARRIS_STAGGER=n: odd workgroups sleep n x 8k cycles before their first tile (A/B)
-  static const int stagger = diag_int("SFMFEAT_HARRIS_STAGGER", 0);
+  static const int stagger = env_int(SFM_DIAG_ENV("SFMFEAT_HARRIS_STAGGER"), 0);
   g.stagger = stagger;
   // SFMFEAT_HARRIS_PP=1: product planes in LDS (form 3) instead of gradient planes (A/B)
-  static const int pp = diag_int("SFMFEAT_HARRIS_PP", kHarrisProductPlanes);
+  static const int pp = env_int(SFM_DIAG_ENV("SFMFEAT_HARRIS_PP"), kHarrisProductPlanes);
   // SFMFEAT_HARRIS_MF=1: window sums on the matrix pipe (form 4) for the levels that take
   // form 0; 2: for every level; 3 / 4: S_xy on MFMA beside the VALU (form 5), form-0 levels
   // / every level
-  static const int mf = diag_int("SFMFEAT_HARRIS_MF", kHarrisMfma);
+  static const int mf = env_int(SFM_DIAG_ENV("SFMFEAT_HARRIS_MF"), kHarrisMfma);
   if constexpr (KS == 7) {  // the alternative forms are built for the 7 x 7 window only
     // the fused pyramid (levels with down[0] set) is validated in form 0 only
     bool fused = false;
@@ -912,10 +903,7 @@ void launch_harris_levels(const HarrisLevels& g, int B, const float* d_gauss, in
     case 6: launch_ks<6>(g, B, d_gauss, alpha, st); break;
     case 7: {
       // SFMFEAT_HARRIS_ABL=1|2: timing ablations inside the pipeline (results are wrong)
-      static const int abl = [] {
-        const char* e = SFM_ABLATION_ENV("SFMFEAT_HARRIS_ABL");
-        return e ? atoi(e) : 0;
-      }();
+      static const int abl = env_int(SFM_ABLATION_ENV("SFMFEAT_HARRIS_ABL"), 0);
       if (abl == 1) launch_ks<7, 1>(g, B, d_gauss, alpha, st);
       else if (abl == 2) launch_ks<7, 2>(g, B, d_gauss, alpha, st);
       else launch_ks<7>(g, B, d_gauss, alpha, st);

@@ -1,5 +1,5 @@
 // kernels.h — launcher declarations and the per-plane bookkeeping shared between the
-// host orchestration (sfmfeat.cpp) and the gfx950 kernels.
+// host orchestration (api_*.hip) and the gfx950 kernels.
 //
 // A "plane" is one pyramid level of one image.  All B planes of a level are stored
 // contiguously ([B][h][w]) and are processed by one launch per stage.

@@ -79,7 +79,7 @@ def test_certified_select_equals_exact_and_oracle(H, W, pp):
 def test_1080p_planes_certify():
     """At the metric's configuration every plane of textured frames certifies, except the
     levels too small to hold ~k window maxima (h*w < 64 k), which go straight to the exact
-    path by design (sfmfeat_api.hip, extract_impl)."""
+    path by design (api_extract.hip extract_impl; extract_layout.h's size-only `exact` flag)."""
     pp = P_OCT
     imgs = np.stack([synth.make_frame(1080, 1920, 1234, i) for i in range(2)])
     xy, desc, cnt, (fb, tot) = run(imgs, pp, exact=False)
@@ -101,7 +101,7 @@ def test_scale_1_1_four_levels_selection_regions_vs_oracle(exact, serial):
     regions (one per level, packed after the aux stream's) and the serial layout (every
     level from 0) cover far more than 2 x B x A0 slots.  Noise planes give C > 2048
     candidates, so the tie lists are written; the exact path writes the median lists.
-    Every plane must still equal the oracle (sfmfeat_api.hip reserve_impl sizes both)."""
+    Every plane must still equal the oracle (extract_layout.h sizes and places both)."""
     pp = dict(P_MAIN, num_interest_points=2000, pyramid_level=4, pyramid_scale_factor=1.1)
     H, W = 360, 640
     rng = np.random.default_rng(11)
