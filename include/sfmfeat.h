@@ -195,6 +195,34 @@ int32_t sfm_ransac_find_inliers_dev(sfm_ctx* ctx, const int32_t* pts, const int3
                                     double threshold, int32_t* out_pts, int32_t* out_n, int32_t* out_iter,
                                     void* stream);
 
+/* CameraPose.ransac_camera_motion (SFM.py:38-103), the initial pair's own RANSAC
+ * (Runner.py:202-208, :349-351), for P correspondence sets at once.
+ * pts/npts/npts_host/nmax/iters/threshold/out_pts/out_n/out_iter as sfm_ransac_find_inliers_dev;
+ * K [P][2][9] (K1, K2 row-major), base [P][12] (R_base row-major, then T_base), host doubles;
+ * out_R [P][9], out_t [P][3] host doubles (untouched where out_iter = -1).
+ * out_n: -1 for n < 8 (four Nones), 0 when no sample had both a valid pose
+ * (_check_valid_pose, SFM.py:105-124) and an inlier.  Synchronises the stream. */
+int32_t sfm_ransac_camera_motion_dev(sfm_ctx* ctx, const int32_t* pts, const int32_t* npts,
+                                     const int32_t* npts_host, int32_t P, int32_t nmax, int32_t iters,
+                                     double threshold, const double* K, const double* base, int32_t* out_pts,
+                                     int32_t* out_n, int32_t* out_iter, double* out_R, double* out_t,
+                                     void* stream);
+
+/* The same for one pair through host pointers: p1, p2 n x 2 int64, K1, K2, R_base [9]
+ * row-major, T_base [3]; R [9], t [3] written when *n_out > 0; in1, in2, n_out, best_iter as
+ * sfm_ransac_find_inliers (n_out -1 for n < 8, 0 when nothing won). */
+int32_t sfm_ransac_camera_motion(sfm_ctx* ctx, const int64_t* p1, const int64_t* p2, int64_t n,
+                                 const double* K1, const double* K2, const double* R_base,
+                                 const double* T_base, int32_t iters, double threshold, double* R, double* t,
+                                 int64_t* in1, int64_t* in2, int64_t* n_out, int32_t* best_iter);
+
+/* CameraPose.triangulate_point (SFM.py:239-253) over N points (Runner.py:208, :278), or
+ * CameraPose.triangulate_points (SFM.py:292-305) with normalize = 1 (the Hartley transforms of
+ * both sets computed on the device).  Device pointers: x1, x2 [N][2], P1, P2 [12] row-major
+ * 3 x 4, X [N][3], all float64.  Enqueued on `stream`, not synchronised. */
+int32_t sfm_triangulate_dev(sfm_ctx* ctx, const double* x1, const double* x2, int64_t N, const double* P1,
+                            const double* P2, int32_t normalize, double* X, void* stream);
+
 /* sfm_ingest_rgb for B frames: rgb [B][H][W][3] uint8 -> gray [B][H2][W2] float32. */
 int32_t sfm_ingest_rgb_dev(sfm_ctx* ctx, const uint8_t* rgb, int32_t B, int32_t H, int32_t W,
                            int32_t H2, int32_t W2, float* gray, void* stream);
@@ -402,6 +430,11 @@ int32_t sfm_copy_wg(void* dst, const void* src, int64_t bytes, int32_t workgroup
  * (image x level) that took the exact-median path, and planes in total.  The default
  * certified select decides the others from the Harris histogram alone. */
 int32_t sfm_debug_select_stats(sfm_ctx* ctx, int32_t* fallback_planes, int32_t* total_planes);
+/* The last sfm_ransac_camera_motion* call's per-sample result -> cand_idx [P][iters] (host):
+ * the index of the sample's valid candidate in this library's order (R1, T), (R1, -T),
+ * (R2, T), (R2, -T), or -1 (none valid, or the sample had no inlier and was skipped).
+ * entries must be that call's P * iters (else SFM_ESTATE). */
+int32_t sfm_debug_pose_candidates(sfm_ctx* ctx, int32_t* cand_idx, int64_t entries);
 /* Level l's R maps (what 0) or level images (what 1) of the last extraction -> out [B][h][w]
  * (device, on `stream`; diagnostics). */
 int32_t sfm_debug_copy_level(sfm_ctx* ctx, int32_t l, int32_t what, float* out, void* stream);

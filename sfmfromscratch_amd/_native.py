@@ -26,6 +26,7 @@ _fp = ctypes.POINTER(ctypes.c_float)
 _i64p = ctypes.POINTER(ctypes.c_int64)
 _i32p = ctypes.POINTER(ctypes.c_int32)
 _u8p = ctypes.POINTER(ctypes.c_uint8)
+_dp = ctypes.POINTER(ctypes.c_double)
 _vp = ctypes.c_void_p
 
 # exported symbol -> (restype, argtypes); every symbol of include/sfmfeat.h
@@ -51,6 +52,14 @@ SIGNATURES = {
     "sfm_ransac_sample_indices": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, ctypes.c_uint32, _i32p]),
     "sfm_ransac_find_inliers_dev": (ctypes.c_int32, [_vp, _vp, _vp, _i32p, ctypes.c_int32, ctypes.c_int32,
                                                      ctypes.c_int32, ctypes.c_double, _vp, _vp, _vp, _vp]),
+    "sfm_ransac_camera_motion_dev": (ctypes.c_int32, [_vp, _vp, _vp, _i32p, ctypes.c_int32, ctypes.c_int32,
+                                                      ctypes.c_int32, ctypes.c_double, _dp, _dp, _vp, _vp, _vp,
+                                                      _dp, _dp, _vp]),
+    "sfm_ransac_camera_motion": (ctypes.c_int32, [_vp, _i64p, _i64p, ctypes.c_int64, _dp, _dp, _dp, _dp,
+                                                  ctypes.c_int32, ctypes.c_double, _dp, _dp, _i64p, _i64p, _i64p,
+                                                  _i32p]),
+    "sfm_triangulate_dev": (ctypes.c_int32, [_vp, _vp, _vp, ctypes.c_int64, _vp, _vp, ctypes.c_int32, _vp, _vp]),
+    "sfm_debug_pose_candidates": (ctypes.c_int32, [_vp, _i32p, ctypes.c_int64]),
     "sfm_ingest_rgb_dev": (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                             ctypes.c_int32, ctypes.c_int32, _vp, _vp]),
     "sfm_extract_batch_dev": (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp,
@@ -323,6 +332,37 @@ class Context:
         if k.value < 0:
             return None
         return o1[:k.value], o2[:k.value], int(bi.value)
+
+    def ransac_camera_motion(self, p1, p2, K1, K2, R_base, T_base, threshold: float, iters: int):
+        """-> (R (3,3), t (3,), in1 (k,2) int64, in2 (k,2) int64, best_iter); R, t None when nothing
+        won (k = 0); None when n < 8."""
+        p1 = np.ascontiguousarray(p1, np.int64).reshape(-1, 2)
+        p2 = np.ascontiguousarray(p2, np.int64).reshape(-1, 2)
+        mats = [np.ascontiguousarray(m, np.float64).reshape(-1) for m in (K1, K2, R_base, T_base)]
+        if [m.size for m in mats] != [9, 9, 9, 3]:
+            raise ValueError("K1, K2, R_base are 3 x 3 and T_base has 3 entries")
+        n = p1.shape[0]
+        o1 = np.empty((max(n, 1), 2), np.int64)
+        o2 = np.empty((max(n, 1), 2), np.int64)
+        R = np.empty((3, 3), np.float64)
+        t = np.empty(3, np.float64)
+        k = ctypes.c_int64(0)
+        bi = ctypes.c_int32(-1)
+        check(self.lib.sfm_ransac_camera_motion(
+            self.handle, p1.ctypes.data_as(_i64p), p2.ctypes.data_as(_i64p), n, *(m.ctypes.data_as(_dp) for m in mats),
+            int(iters), ctypes.c_double(threshold), R.ctypes.data_as(_dp), t.ctypes.data_as(_dp),
+            o1.ctypes.data_as(_i64p), o2.ctypes.data_as(_i64p), ctypes.byref(k), ctypes.byref(bi)), self.handle)
+        if k.value < 0:
+            return None
+        if k.value == 0:
+            return None, None, o1[:0], o2[:0], -1
+        return R, t, o1[:k.value], o2[:k.value], int(bi.value)
+
+    def pose_candidates(self, P: int, iters: int) -> np.ndarray:
+        """[P, iters] int32: the valid candidate of each sample of the last pose call, or -1."""
+        out = np.empty((P, iters), np.int32)
+        check(self.lib.sfm_debug_pose_candidates(self.handle, out.ctypes.data_as(_i32p), P * iters), self.handle)
+        return out
 
     # -------- device-pointer API (throughput path; pointers are ints) --------
     def ingest_rgb_dev(self, rgb_ptr: int, B: int, H: int, W: int, H2: int, W2: int, gray_ptr: int,

@@ -1,5 +1,6 @@
 // api_stage1.hip — the stages around detect + describe + match: frame ingest (workspace
-// c->ingest) and RANSAC inlier search (workspace c->ransac).
+// c->ingest), RANSAC inlier search (workspace c->ransac) and the initial pair's pose RANSAC
+// with triangulation (workspace c->pose, on top of c->ransac's samples, F and counts).
 #include <atomic>
 #include <thread>
 
@@ -87,8 +88,19 @@ void ransac_prefetch_streams(sfm_ctx* c, const std::vector<int>& ns, int iters) 
   }
 }
 
+// host K [P][18] and base [P][12] of a pose call, its host outputs
+struct PoseJob {
+  const double* K;
+  const double* base;
+  double* out_R;
+  double* out_t;
+};
+
+// pose == nullptr: find_inliers; else ransac_camera_motion (the cheirality check between the
+// count and the selection, the winners' (R, t) copied to the job's host outputs)
 int ransac_impl(sfm_ctx* c, const int32_t* pts, const int32_t* npts_dev, const int32_t* npts_host, int P, int nmax,
-                int iters, double thr, int32_t* out_pts, int32_t* out_n, int32_t* out_iter, hipStream_t st) {
+                int iters, double thr, int32_t* out_pts, int32_t* out_n, int32_t* out_iter, hipStream_t st,
+                const PoseJob* pose = nullptr) {
   // sample streams (host replay of numpy's RandomState; identical for equal n)
   {
     std::vector<int> ns;
@@ -129,11 +141,86 @@ int ransac_impl(sfm_ctx* c, const int32_t* pts, const int32_t* npts_dev, const i
   if ((rc = ensure(c, r.counts, (size_t)P * std::max(iters, 1) * 4))) return rc;
   HIPCHK(c, hipMemcpyAsync(r.idx.p, all.data(), all.size() * 4, hipMemcpyHostToDevice, st));
   HIPCHK(c, hipMemcpyAsync(r.off.p, off.data(), (size_t)P * 4, hipMemcpyHostToDevice, st));
+  if (pose) {
+    PoseWs& w = c->pose;
+    const size_t slots = (size_t)P * std::max(iters, 1);
+    if ((rc = ensure(c, w.K, (size_t)P * 18 * 8))) return rc;
+    if ((rc = ensure(c, w.base, (size_t)P * 12 * 8))) return rc;
+    if ((rc = ensure(c, w.cand, slots * 21 * 8))) return rc;
+    if ((rc = ensure(c, w.cand_idx, slots * 4))) return rc;
+    if ((rc = ensure(c, w.Rt, (size_t)P * 12 * 8))) return rc;
+    HIPCHK(c, hipMemcpyAsync(w.K.p, pose->K, (size_t)P * 18 * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(w.base.p, pose->base, (size_t)P * 12 * 8, hipMemcpyHostToDevice, st));
+    launch_ransac_pose(pts, npts_dev, nmax, P, as<int32_t>(r.idx), as<int32_t>(r.off), iters, thr, as<double>(w.K),
+                       as<double>(w.base), as<double>(r.F), as<int32_t>(r.counts), as<double>(w.cand),
+                       as<int32_t>(w.cand_idx), out_pts, out_n, out_iter, as<double>(w.Rt), st);
+    HIPCHK(c, hipGetLastError());
+    w.last_entries = (int64_t)P * iters;
+    std::vector<int32_t> oit(P);
+    std::vector<double> rt((size_t)P * 12);
+    HIPCHK(c, hipMemcpyAsync(oit.data(), out_iter, (size_t)P * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(rt.data(), w.Rt.p, rt.size() * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    for (int p = 0; p < P; ++p) {
+      if (oit[p] < 0) continue;  // no pose: the caller's R, t stay as they are
+      std::copy(rt.begin() + 12 * p, rt.begin() + 12 * p + 9, pose->out_R + 9 * p);
+      std::copy(rt.begin() + 12 * p + 9, rt.begin() + 12 * p + 12, pose->out_t + 3 * p);
+    }
+    return SFM_OK;
+  }
   // iters == 0 still launches the select kernel: it writes every pair's empty / None result
   launch_ransac(pts, npts_dev, nmax, P, as<int32_t>(r.idx), as<int32_t>(r.off), iters, thr, as<double>(r.F),
                 as<int32_t>(r.counts), out_pts, out_n, out_iter, st);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(st));  // the host index buffers above are stack-owned
+  return SFM_OK;
+}
+
+// one pair through host pointers (int64 points): staging, ransac_impl, the inliers copied back
+int ransac_host_pair(sfm_ctx* c, const int64_t* p1, const int64_t* p2, int64_t n, int iters, double threshold,
+                     int64_t* in1, int64_t* in2, int64_t* n_out, int32_t* best_iter, const PoseJob* pose) {
+  if (n > INT32_MAX / 4) return set_err(c, SFM_EINVAL, "too many correspondences");
+  HIPCHK(c, hipSetDevice(c->device));
+  *n_out = -1;
+  if (n < 8) return SFM_OK;  // the reference returns (None, None, None, None)
+  const int nmax = (int)n;
+  std::vector<int32_t> h((size_t)nmax * 4);
+  for (int64_t i = 0; i < n; ++i) {
+    h[4 * i + 0] = (int32_t)p1[2 * i];
+    h[4 * i + 1] = (int32_t)p1[2 * i + 1];
+    h[4 * i + 2] = (int32_t)p2[2 * i];
+    h[4 * i + 3] = (int32_t)p2[2 * i + 1];
+  }
+  int rc;
+  RansacWs& r = c->ransac;
+  if ((rc = ensure(c, r.pts, h.size() * 4))) return rc;
+  if ((rc = ensure(c, r.npts, 16))) return rc;
+  if ((rc = ensure(c, r.out, h.size() * 4))) return rc;
+  if ((rc = ensure(c, r.on, 16))) return rc;
+  if ((rc = ensure(c, r.oit, 16))) return rc;
+  hipStream_t st;
+  if ((rc = host_stream(c, &st))) return rc;
+  const int32_t nn = (int32_t)n;
+  HIPCHK(c, hipMemcpyAsync(r.pts.p, h.data(), h.size() * 4, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(r.npts.p, &nn, 4, hipMemcpyHostToDevice, st));
+  if ((rc = ransac_impl(c, as<int32_t>(r.pts), as<int32_t>(r.npts), &nn, 1, nmax, iters, threshold,
+                        as<int32_t>(r.out), as<int32_t>(r.on), as<int32_t>(r.oit), st, pose)))
+    return rc;
+  int32_t k = 0, bi = -1;
+  HIPCHK(c, hipMemcpyAsync(&k, r.on.p, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(&bi, r.oit.p, 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  if (k > n) return set_err(c, SFM_EDEVICE, "inlier count above the correspondence count");
+  if (k > 0) {
+    std::vector<int32_t> o((size_t)k * 4);
+    HIPCHK(c, hipMemcpy(o.data(), r.out.p, o.size() * 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < k; ++i) {
+      if (in1) { in1[2 * i] = o[4 * i]; in1[2 * i + 1] = o[4 * i + 1]; }
+      if (in2) { in2[2 * i] = o[4 * i + 2]; in2[2 * i + 1] = o[4 * i + 3]; }
+    }
+  }
+  *n_out = k;
+  if (best_iter) *best_iter = bi;
   return SFM_OK;
 }
 
@@ -195,48 +282,58 @@ int32_t sfm_ransac_find_inliers_dev(sfm_ctx* c, const int32_t* pts, const int32_
 int32_t sfm_ransac_find_inliers(sfm_ctx* c, const int64_t* p1, const int64_t* p2, int64_t n, int32_t iters,
                                 double threshold, int64_t* in1, int64_t* in2, int64_t* n_out, int32_t* best_iter) {
   if (!c || !n_out || n < 0 || iters < 0 || (n > 0 && (!p1 || !p2))) return SFM_EINVAL;
-  if (n > INT32_MAX / 4) return set_err(c, SFM_EINVAL, "too many correspondences");
+  return ransac_host_pair(c, p1, p2, n, iters, threshold, in1, in2, n_out, best_iter, nullptr);
+}
+
+int32_t sfm_ransac_camera_motion_dev(sfm_ctx* c, const int32_t* pts, const int32_t* npts, const int32_t* npts_host,
+                                     int32_t P, int32_t nmax, int32_t iters, double threshold, const double* K,
+                                     const double* base, int32_t* out_pts, int32_t* out_n, int32_t* out_iter,
+                                     double* out_R, double* out_t, void* stream) {
+  if (!c || !pts || !npts || !npts_host || !K || !base || !out_pts || !out_n || !out_iter || !out_R || !out_t ||
+      P < 1 || nmax < 1 || iters < 0)
+    return SFM_EINVAL;
   HIPCHK(c, hipSetDevice(c->device));
-  *n_out = -1;
-  if (n < 8) return SFM_OK;  // the reference returns (None, None, None, None)
-  const int nmax = (int)n;
-  std::vector<int32_t> h((size_t)nmax * 4);
-  for (int64_t i = 0; i < n; ++i) {
-    h[4 * i + 0] = (int32_t)p1[2 * i];
-    h[4 * i + 1] = (int32_t)p1[2 * i + 1];
-    h[4 * i + 2] = (int32_t)p2[2 * i];
-    h[4 * i + 3] = (int32_t)p2[2 * i + 1];
-  }
+  const PoseJob job{K, base, out_R, out_t};
+  return ransac_impl(c, pts, npts, npts_host, P, nmax, iters, threshold, out_pts, out_n, out_iter,
+                     (hipStream_t)stream, &job);
+}
+
+int32_t sfm_ransac_camera_motion(sfm_ctx* c, const int64_t* p1, const int64_t* p2, int64_t n, const double* K1,
+                                 const double* K2, const double* R_base, const double* T_base, int32_t iters,
+                                 double threshold, double* R, double* t, int64_t* in1, int64_t* in2,
+                                 int64_t* n_out, int32_t* best_iter) {
+  if (!c || !n_out || !K1 || !K2 || !R_base || !T_base || !R || !t || n < 0 || iters < 0 ||
+      (n > 0 && (!p1 || !p2)))
+    return SFM_EINVAL;
+  double Kc[18], base[12];
+  std::copy(K1, K1 + 9, Kc);
+  std::copy(K2, K2 + 9, Kc + 9);
+  std::copy(R_base, R_base + 9, base);
+  std::copy(T_base, T_base + 3, base + 9);
+  const PoseJob job{Kc, base, R, t};
+  return ransac_host_pair(c, p1, p2, n, iters, threshold, in1, in2, n_out, best_iter, &job);
+}
+
+int32_t sfm_debug_pose_candidates(sfm_ctx* c, int32_t* cand_idx, int64_t entries) {
+  if (!c || !cand_idx || entries < 0) return SFM_EINVAL;
+  if (entries != c->pose.last_entries) return set_err(c, SFM_ESTATE, "not the last pose call's P * iters");
+  if (entries == 0) return SFM_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpy(cand_idx, c->pose.cand_idx.p, (size_t)entries * 4, hipMemcpyDeviceToHost));
+  return SFM_OK;
+}
+
+int32_t sfm_triangulate_dev(sfm_ctx* c, const double* x1, const double* x2, int64_t N, const double* P1,
+                            const double* P2, int32_t normalize, double* X, void* stream) {
+  if (!c || N < 0 || !P1 || !P2 || (normalize != 0 && normalize != 1) || (N > 0 && (!x1 || !x2 || !X)))
+    return SFM_EINVAL;
+  if (N > ((int64_t)1 << 37)) return set_err(c, SFM_EINVAL, "too many points");
+  if (N == 0) return SFM_OK;
+  HIPCHK(c, hipSetDevice(c->device));
   int rc;
-  RansacWs& r = c->ransac;
-  if ((rc = ensure(c, r.pts, h.size() * 4))) return rc;
-  if ((rc = ensure(c, r.npts, 16))) return rc;
-  if ((rc = ensure(c, r.out, h.size() * 4))) return rc;
-  if ((rc = ensure(c, r.on, 16))) return rc;
-  if ((rc = ensure(c, r.oit, 16))) return rc;
-  hipStream_t st;
-  if ((rc = host_stream(c, &st))) return rc;
-  const int32_t nn = (int32_t)n;
-  HIPCHK(c, hipMemcpyAsync(r.pts.p, h.data(), h.size() * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync(r.npts.p, &nn, 4, hipMemcpyHostToDevice, st));
-  if ((rc = ransac_impl(c, as<int32_t>(r.pts), as<int32_t>(r.npts), &nn, 1, nmax, iters, threshold,
-                        as<int32_t>(r.out), as<int32_t>(r.on), as<int32_t>(r.oit), st)))
-    return rc;
-  int32_t k = 0, bi = -1;
-  HIPCHK(c, hipMemcpyAsync(&k, r.on.p, 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipMemcpyAsync(&bi, r.oit.p, 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipStreamSynchronize(st));
-  if (k > n) return set_err(c, SFM_EDEVICE, "inlier count above the correspondence count");
-  if (k > 0) {
-    std::vector<int32_t> o((size_t)k * 4);
-    HIPCHK(c, hipMemcpy(o.data(), r.out.p, o.size() * 4, hipMemcpyDeviceToHost));
-    for (int i = 0; i < k; ++i) {
-      if (in1) { in1[2 * i] = o[4 * i]; in1[2 * i + 1] = o[4 * i + 1]; }
-      if (in2) { in2[2 * i] = o[4 * i + 2]; in2[2 * i + 1] = o[4 * i + 3]; }
-    }
-  }
-  *n_out = k;
-  if (best_iter) *best_iter = bi;
+  if ((rc = ensure(c, c->pose.tri, 30 * 8))) return rc;
+  launch_triangulate(x1, x2, N, P1, P2, normalize != 0, as<double>(c->pose.tri), X, (hipStream_t)stream);
+  HIPCHK(c, hipGetLastError());
   return SFM_OK;
 }
 

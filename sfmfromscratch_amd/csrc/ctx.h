@@ -4,7 +4,7 @@
 //   api_ctx.hip      params, create / destroy, setters, gate, stream
 //   api_extract.hip  c->ex     (pyramid .. descriptors; layout in extract_layout.h)
 //   api_match.hip    c->match  (operands + their owner record, per-pair buffers)
-//   api_stage1.hip   c->ingest, c->ransac
+//   api_stage1.hip   c->ingest, c->ransac, c->pose
 //   api_profile.hip  c->prof   (stage events, Harris spans, the sfm_debug_* reads)
 #pragma once
 
@@ -149,6 +149,14 @@ struct RansacWs {
   DevBuf idx, off, F, counts, pts, npts, out, on, oit;
 };
 
+// Pose (sfm_ransac_camera_motion*, sfm_triangulate_dev): per-pair intrinsics and base pose,
+// per-sample candidates (R1, R2, T) and the valid candidate's index, the winners' (R, t);
+// the sample streams, F and counts are RansacWs's
+struct PoseWs {
+  DevBuf K, base, cand, cand_idx, Rt, tri;
+  int64_t last_entries = 0;  // P * iters of the last call (sfm_debug_pose_candidates)
+};
+
 struct sfm_ctx {
   CtxStreams s;  // (first: outlives the workspaces below)
   int device = 0;
@@ -166,6 +174,7 @@ struct sfm_ctx {
   MatchWs match;
   IngestWs ingest;
   RansacWs ransac;
+  PoseWs pose;
   // the workspaces free their buffers after this body, the streams and events go last
   ~sfm_ctx() {
     (void)hipSetDevice(device);

@@ -204,6 +204,27 @@ void ransac_sample_indices(int n, int iters, uint32_t seed, int32_t* out);
 void launch_ransac(const int32_t* pts, const int32_t* npts, int nmax, int P, const int32_t* idx,
                    const int32_t* idx_off, int iters, double thr, double* Fs, int32_t* counts, int32_t* out_pts,
                    int32_t* out_n, int32_t* out_iter, hipStream_t st);
+constexpr int kRansacChunk = 2560;  // points staged in LDS at a time (32 B each)
+
+// pose.hip: CameraPose.ransac_camera_motion (SFM.py:38-124) on top of the RANSAC launches, and
+// triangulate_point / triangulate_points (SFM.py:239-253, 292-305).  Kc [P][2][9] (K1, K2),
+// base [P][12] (R_base, T_base), cand [P][iters][21] (R1, R2, T), cand_idx [P][iters] (the
+// valid candidate of each sample or -1), out_Rt [P][12]; all device, row-major float64.
+void launch_ransac_pose(const int32_t* pts, const int32_t* npts, int nmax, int P, const int32_t* idx,
+                        const int32_t* idx_off, int iters, double thr, const double* Kc, const double* base,
+                        double* Fs, int32_t* counts, double* cand, int32_t* cand_idx, int32_t* out_pts,
+                        int32_t* out_n, int32_t* out_iter, double* out_Rt, hipStream_t st);  // ransac.hip
+void launch_pose_candidates(const double* Fs, const int32_t* npts, const double* Kc, int P, int iters,
+                            double* cand, hipStream_t st);
+void launch_pose_cheirality(const int32_t* pts, const int32_t* npts, int nmax, int P, const double* Kc,
+                            const double* base, const double* cand, int iters, int32_t* counts,
+                            int32_t* cand_idx, hipStream_t st);
+void launch_pose_gather(const int32_t* out_iter, const double* cand, const int32_t* cand_idx, int P, int iters,
+                        double* out_Rt, hipStream_t st);
+// x1, x2 [N][2], P1, P2 [12], X [N][3]; normalize: Hartley transforms computed on the device
+// (scratch30: 30 doubles of workspace)
+void launch_triangulate(const double* x1, const double* x2, int64_t N, const double* P1, const double* P2,
+                        bool normalize, double* scratch30, double* X, hipStream_t st);
 
 // ingest.hip: PIL BICUBIC resize of [B][H][W][3] u8 RGB to H2 x W2 + /255 + _rgb2gray
 // (Runner.py:33-46) -> [B][H2][W2] float32; tmp holds [B][H][W2][3] u8.  Tables from

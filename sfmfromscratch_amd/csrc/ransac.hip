@@ -386,7 +386,6 @@ SFM_DEV EpiThr epi_thr(double thr) {  // thr <= 0 (or NaN): nothing is an inlier
 // sweep; the pair's points are staged in LDS as float64 (x1, y1, x2, y2) in chunks of
 // kRansacChunk points and every lane reads the same point (a broadcast) — no per-sample
 // reduction, F reload or conversion.  Any n: larger sets take several chunks.
-constexpr int kRansacChunk = 2560;
 __global__ void __launch_bounds__(256) k_ransac_count(const int32_t* __restrict__ pts,
                                                       const int32_t* __restrict__ npts, int nmax,
                                                       const double* __restrict__ Fs, int iters, double thr,
@@ -495,6 +494,31 @@ void launch_ransac(const int32_t* pts, const int32_t* npts, int nmax, int P, con
   // result (n >= 8) or None (n < 8), out_iter -1
   hipLaunchKernelGGL(k_ransac_select, dim3(P), dim3(256), 0, st, pts, npts, nmax, Fs, counts, iters, thr, out_pts,
                      out_n, out_iter);
+}
+
+// CameraPose.ransac_camera_motion (SFM.py:38-103): the same F and count launches, then the
+// pose candidates and their cheirality check (pose.hip), which zeroes the count of every
+// sample without a valid pose, then the same selection and the winner's (R, t).
+void launch_ransac_pose(const int32_t* pts, const int32_t* npts, int nmax, int P, const int32_t* idx,
+                        const int32_t* idx_off, int iters, double thr, const double* Kc, const double* base,
+                        double* Fs, int32_t* counts, double* cand, int32_t* cand_idx, int32_t* out_pts,
+                        int32_t* out_n, int32_t* out_iter, double* out_Rt, hipStream_t st) {
+  if (iters > 0) {
+    hipLaunchKernelGGL(k_ransac_F, dim3((iters + 127) / 128, P), dim3(128), 0, st, pts, npts, nmax, idx, idx_off,
+                       iters, Fs);
+    static const bool lds_attr = [] {
+      return hipFuncSetAttribute((const void*)k_ransac_count, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 kRansacChunk * 32) == hipSuccess;
+    }();
+    (void)lds_attr;
+    hipLaunchKernelGGL(k_ransac_count, dim3((iters + 255) / 256, P), dim3(256),
+                       (size_t)std::min(nmax, kRansacChunk) * 32, st, pts, npts, nmax, Fs, iters, thr, counts);
+    launch_pose_candidates(Fs, npts, Kc, P, iters, cand, st);
+    launch_pose_cheirality(pts, npts, nmax, P, Kc, base, cand, iters, counts, cand_idx, st);
+  }
+  hipLaunchKernelGGL(k_ransac_select, dim3(P), dim3(256), 0, st, pts, npts, nmax, Fs, counts, iters, thr, out_pts,
+                     out_n, out_iter);
+  if (iters > 0) launch_pose_gather(out_iter, cand, cand_idx, P, iters, out_Rt, st);
 }
 
 }  // namespace sfm

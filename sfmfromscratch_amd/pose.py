@@ -10,6 +10,9 @@ values as the reference (ransac.hip has the numerics):
 * the first sample with the most inliers wins; its inliers are returned in input order
   as p1[mask], p2[mask]; no inliers at all gives the reference's empty float64 arrays;
   fewer than 8 correspondences gives its (None, None, None, None).
+
+Below: the consumer of the pair the filter leaves alone, CameraPose.ransac_camera_motion
+(SFM.py:38-124), and the linear triangulation it is built from (pose.hip).
 """
 from __future__ import annotations
 
@@ -107,3 +110,144 @@ def find_inliers_batch(pairs, threshold=1.0, max_iterations=1000, device: int = 
         else:
             res[k] = (op[p, :n, :2].astype(a.dtype), op[p, :n, 2:].astype(b.dtype))
     return res
+
+
+# ---------------- the initial pair: pose RANSAC and triangulation (pose.hip) ----------------
+
+def calculate_projection_matrix(R, t, K):
+    """CameraPose.calculate_projection_matrix (SFM.py:307-309)."""
+    return np.asarray(K) @ np.hstack([np.asarray(R), np.asarray(t).reshape(-1, 1)])
+
+
+def _check_pose_points(p1, p2, what):
+    if p1.shape != p2.shape or p1.ndim != 2 or p1.shape[1] != 2:
+        raise ValueError(f"{what}: pts1 and pts2 must both be [n, 2]")
+    if not (np.array_equal(p1, np.round(p1)) and np.array_equal(p2, np.round(p2))):
+        raise ValueError(f"{what}: ransac_camera_motion takes integer pixel coordinates (Runner.py:423-434)")
+
+
+def ransac_camera_motion(pts1, pts2, K1, K2, R_base, T_base, threshold=1.0, max_iterations=1000, device: int = 0):
+    """Drop-in for CameraPose(pts1, pts2, K1, K2).ransac_camera_motion(R_base, T_base, ...)
+    (SFM.py:38-103), the initial pair's own RANSAC (Runner.py:202-208): the samples and
+    inlier test of `find_inliers`, and among the samples one of whose four (R, t)
+    candidates puts every triangulated correspondence in front of both cameras
+    (_check_valid_pose, SFM.py:105-124) the first with the most inliers.  Returns
+    (R, t, inliers1, inliers2); (None, None, None, None) below 8 correspondences;
+    (None, None, array([]), array([])) when no sample won.
+
+    Integer pixel coordinates only, the divergence documented at `find_inliers`."""
+    p1 = np.asarray(pts1)
+    p2 = np.asarray(pts2)
+    if len(p1) < 8:
+        return None, None, None, None  # SFM.py:42-43
+    _check_pose_points(p1, p2, "ransac_camera_motion")
+    ctx = context_for(_abi.params_from_dict({}, _abi.SFM_MODE_NAIVE), device)
+    R, t, in1, in2, _ = ctx.ransac_camera_motion(p1, p2, K1, K2, R_base, T_base, float(threshold),
+                                                 int(max_iterations))
+    if len(in1) == 0:
+        return None, None, np.array([]), np.array([])
+    return R, t, in1.astype(p1.dtype, copy=False), in2.astype(p2.dtype, copy=False)
+
+
+def ransac_camera_motion_batch(cases, threshold=1.0, max_iterations=1000, device: int = 0, info=None):
+    """ransac_camera_motion over many correspondence sets in one device pass.
+    cases: [(pts1, pts2, K1, K2, R_base, T_base), ...]; returns the per-case results of
+    `ransac_camera_motion`.  info (optional dict) receives "out_iter" (the winning sample per
+    case, -1 for none) and "candidates" (per case the [iters] valid-candidate index of every
+    sample, -1 for none or for a sample without inliers; None below 8 points)."""
+    import ctypes
+
+    import torch
+    res = [None] * len(cases)
+    todo = []
+    for k, (a, b, K1, K2, Rb, Tb) in enumerate(cases):
+        a, b = np.asarray(a), np.asarray(b)
+        if len(a) < 8:
+            res[k] = (None, None, None, None)
+            continue
+        _check_pose_points(a, b, f"case {k}")
+        Km = np.concatenate([np.asarray(K1, np.float64).reshape(-1), np.asarray(K2, np.float64).reshape(-1)])
+        bm = np.concatenate([np.asarray(Rb, np.float64).reshape(-1), np.asarray(Tb, np.float64).reshape(-1)])
+        if Km.size != 18 or bm.size != 12:
+            raise ValueError(f"case {k}: K1, K2, R_base are 3 x 3 and T_base has 3 entries")
+        todo.append((k, a, b, Km, bm))
+    iters = int(max_iterations)
+    if info is not None:
+        info["out_iter"] = [-1] * len(cases)
+        info["candidates"] = [None] * len(cases)
+    if not todo:
+        return res
+    nmax = max(len(t[1]) for t in todo)
+    P = len(todo)
+    pts = np.zeros((P, nmax, 4), np.int32)
+    npts = np.array([len(t[1]) for t in todo], np.int32)
+    Kh = np.ascontiguousarray(np.stack([t[3] for t in todo]))
+    bh = np.ascontiguousarray(np.stack([t[4] for t in todo]))
+    for p, (_, a, b, _, _) in enumerate(todo):
+        pts[p, :len(a), :2] = a
+        pts[p, :len(a), 2:] = b
+    ctx = context_for(_abi.params_from_dict({}, _abi.SFM_MODE_NAIVE), device)
+    dev = torch.device("cuda", device)
+    d_pts = torch.from_numpy(pts).to(dev)
+    d_n = torch.from_numpy(npts).to(dev)
+    o_pts = torch.zeros_like(d_pts)
+    o_n = torch.zeros(P, dtype=torch.int32, device=dev)
+    o_it = torch.zeros(P, dtype=torch.int32, device=dev)
+    oR = np.zeros((P, 3, 3), np.float64)
+    ot = np.zeros((P, 3), np.float64)
+    dp = ctypes.POINTER(ctypes.c_double)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    check(ctx.lib.sfm_ransac_camera_motion_dev(
+        ctx.handle, d_pts.data_ptr(), d_n.data_ptr(), npts.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), P, nmax,
+        iters, ctypes.c_double(threshold), Kh.ctypes.data_as(dp), bh.ctypes.data_as(dp), o_pts.data_ptr(),
+        o_n.data_ptr(), o_it.data_ptr(), oR.ctypes.data_as(dp), ot.ctypes.data_as(dp), stream or None), ctx.handle)
+    on = o_n.cpu().numpy()
+    oit = o_it.cpu().numpy()
+    op = o_pts.cpu().numpy()
+    cand = ctx.pose_candidates(P, iters) if info is not None else None
+    for p, (k, a, b, _, _) in enumerate(todo):
+        n = int(on[p])
+        if n <= 0:
+            res[k] = (None, None, np.array([]), np.array([]))
+        else:
+            res[k] = (oR[p].copy(), ot[p].copy(), op[p, :n, :2].astype(a.dtype), op[p, :n, 2:].astype(b.dtype))
+        if info is not None:
+            info["out_iter"][k] = int(oit[p])
+            info["candidates"][k] = cand[p].copy()
+    return res
+
+
+def _triangulate(x1, x2, P1, P2, normalize, device):
+    import torch
+    host = not (isinstance(x1, torch.Tensor) and x1.is_cuda)
+    dev = torch.device("cuda", device) if host else x1.device
+
+    def put(a, shape):
+        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a, np.float64))
+        if t.numel() != int(np.prod(shape)):
+            raise ValueError("triangulate: x1, x2 are [n, 2] (or [n, 3] homogeneous) and P1, P2 are 3 x 4")
+        return t.to(device=dev, dtype=torch.float64).contiguous().reshape(shape)
+
+    n = int(x1.shape[0])
+    a, b = put(x1[:, :2], (n, 2)), put(x2[:, :2], (n, 2))
+    A, B = put(P1, (12,)), put(P2, (12,))
+    X = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    ctx = context_for(_abi.params_from_dict({}, _abi.SFM_MODE_NAIVE), dev.index or 0)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    check(ctx.lib.sfm_triangulate_dev(ctx.handle, a.data_ptr(), b.data_ptr(), n, A.data_ptr(), B.data_ptr(),
+                                      1 if normalize else 0, X.data_ptr(), stream or None), ctx.handle)
+    return X.cpu().numpy() if host else X
+
+
+def triangulate(p1, p2, P1, P2, device: int = 0):
+    """[CameraPose.triangulate_point(a, b, P1, P2) for a, b in zip(p1, p2)] (SFM.py:239-253, the
+    loops of Runner.py:208 and :278) in one launch: p1, p2 [n, 2] (a third homogeneous column
+    is ignored), P1, P2 3 x 4 -> [n, 3] float64.  numpy or CPU tensors in, numpy out; device
+    tensors in, a device tensor out."""
+    return _triangulate(p1, p2, P1, P2, False, device)
+
+
+def triangulate_points(x1, x2, P1, P2, device: int = 0):
+    """CameraPose.triangulate_points (SFM.py:292-305): both point sets Hartley-normalised on
+    the device, the transforms applied to P1, P2, then `triangulate`."""
+    return _triangulate(x1, x2, P1, P2, True, device)

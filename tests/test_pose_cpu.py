@@ -1,0 +1,152 @@
+"""CPU: the initial-pair pose RANSAC's pieces that need no device — the numpy restatement
+(tests/pose_ref.py) against the reference's own outputs (tests/golden/pose.npz), the
+admission condition every case of tests/test_gpu_pose.py has to meet, the conditioning of
+the triangulation inputs, and the argument checks of the three new C-ABI calls.
+
+Admission (a case that fails gets another seed; none is masked): the per-iteration
+(count, valid) table is the same (a) with both SVDs replaced by eigen-decompositions of
+E^T E / A^T A — the device's route for E — and (b) with every F perturbed by a relative 1e-10;
+(c) no iteration has more than one valid candidate, so "the first valid candidate" does not
+depend on the order the candidates are listed in (the signs of U[:, 2] and V[:, 2] are the
+SVD routine's choice); (d) no depth is NaN; (e) no point of the winning iteration lies
+within 1e-9 of the threshold."""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+import pytest
+
+from sfmfromscratch_amd import _abi, _native
+from tests import pose_ref as PR
+from tests.golden_util import load
+
+NAMES = list(PR.cases().keys())
+
+
+def case(z, name):
+    g = lambda k: z[f"{name}_{k}"]
+    return (g("p1"), g("p2"), g("K1"), g("K2"), g("Rb"), g("Tb"), float(g("thr")), int(g("iters")))
+
+
+def test_fixture_holds_the_cases_of_pose_ref():
+    z = load("pose.npz")
+    assert list(z["names"]) == NAMES
+    for name, c in PR.cases().items():
+        for a, b in zip(case(z, name), c):
+            assert np.array_equal(a, b), name
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_restatement_equals_reference(name):
+    z = load("pose.npz")
+    R, t, in1, in2, it, tab = PR.ransac_camera_motion(*case(z, name))
+    state = str(z[f"{name}_state"])
+    if state == "none":
+        assert (R, t, in1, in2) == (None, None, None, None)
+        return
+    assert it == int(z[f"{name}_win"])
+    assert np.array_equal(tab["counts"], z[f"{name}_counts"]) and np.array_equal(tab["valid"], z[f"{name}_valid"])
+    if state == "empty":
+        assert R is None and t is None and in1.shape == (0,) and in2.shape == (0,)
+        return
+    assert np.array_equal(in1, z[f"{name}_in1"]) and np.array_equal(in2, z[f"{name}_in2"])
+    assert in1.dtype == z[f"{name}_in1"].dtype
+    assert np.abs(R - z[f"{name}_R"]).max() <= 1e-12 and np.abs(t - z[f"{name}_t"]).max() <= 1e-12
+
+
+def test_golden_cases_return_a_pose():
+    z = load("pose.npz")
+    for i in range(len(PR.GOLDEN)):
+        assert str(z[f"g{i}_state"]) == "pose"
+    assert str(z["random_state"]) == "empty" and str(z["iters0_state"]) == "empty" and str(z["n7_state"]) == "none"
+
+
+@pytest.mark.parametrize("name", [n for n in NAMES if n != "n7"])
+def test_admission_condition(name):
+    z = load("pose.npz")
+    c = case(z, name)
+    tab = PR.table(*c)
+    eig = PR.table(*c, route="eig")
+    per = PR.table(*c, f_noise=1e-10)
+    for other, what in ((eig, "(a) eigen-decompositions"), (per, "(b) perturbed F")):
+        assert np.array_equal(tab["counts"], other["counts"]), what
+        assert np.array_equal(tab["valid"].any(1), other["valid"].any(1)), what
+        assert np.array_equal(tab["valid"].sum(1), other["valid"].sum(1)), what
+    assert tab["valid"].sum(1).max(initial=0) <= 1, "(c) more than one valid candidate"
+    assert not tab["nan_depth"] and not eig["nan_depth"], "(d) NaN depth"
+    it, cand = PR.winner(tab)
+    assert (it, cand >= 0) == PR.winner(eig)[:1] + (PR.winner(eig)[1] >= 0,)
+    if it >= 0:
+        assert np.abs(tab["dist"][it] - c[6]).min() > 1e-9, "(e) a point at the threshold"
+        # the winner's pose by the two routes (the candidate's index may differ, the pose not)
+        ce = PR.winner(eig)[1]
+        assert np.abs(tab["R"][it, cand] - eig["R"][it, ce]).max() < 1e-12
+        assert np.abs(tab["T"][it, cand] - eig["T"][it, ce]).max() < 1e-12
+
+
+def test_triangulation_restatement_and_conditioning():
+    """The restatement equals the reference's triangulate_point / triangulate_points, and at
+    most 2 % of the points the GPU test triangulates have sigma3 / sigma4 < 10 (those are
+    left out of its X comparison)."""
+    z = load("pose.npz")
+    p1, p2, P1, P2 = z["tri_p1"], z["tri_p2"], z["tri_P1"], z["tri_P2"]
+    X, gap = PR.triangulate(p1, p2, P1, P2)
+    assert np.abs(X - z["tri_X"]).max() <= 1e-9 * np.abs(z["tri_X"]).max()
+    assert (gap < 10).mean() <= 0.02
+    for N in PR.TRI_SIZES[1:]:
+        Xn, gapn = PR.triangulate_points(p1[:N], p2[:N], P1, P2)
+        assert np.abs(Xn - z[f"tri_Xn{N}"]).max() <= 1e-9 * np.abs(z[f"tri_Xn{N}"]).max()
+        assert (gapn < 10).mean() <= 0.02
+    for name in NAMES:
+        if f"{name}_X" not in z:
+            continue
+        Pa = z[f"{name}_K1"] @ np.hstack([z[f"{name}_Rb"], z[f"{name}_Tb"].reshape(3, 1)])
+        Pb = z[f"{name}_K2"] @ np.hstack([z[f"{name}_R"], z[f"{name}_t"].reshape(3, 1)])
+        for norm, key in ((PR.triangulate, "X"), (PR.triangulate_points, "Xn")):
+            X, gap = norm(z[f"{name}_in1"], z[f"{name}_in2"], Pa, Pb)
+            ref = z[f"{name}_{key}"]
+            ok = gap >= 10
+            assert (~ok).mean() <= 0.02, (name, key)
+            rel = np.linalg.norm(X - ref, axis=1) / np.linalg.norm(ref, axis=1)
+            assert rel[ok].max() <= 1e-9, (name, key)
+
+
+def test_new_calls_reject_bad_arguments_without_a_device():
+    """SFM_EINVAL comes before any HIP call or use of the context: `fake` is not a context,
+    just a non-null pointer that a premature dereference would trip over."""
+    L = _native.load_library()
+    fake = ctypes.cast(ctypes.create_string_buffer(8192), ctypes.c_void_p)
+    i32 = (ctypes.c_int32 * 4)()
+    i64 = (ctypes.c_int64 * 64)()
+    d = (ctypes.c_double * 32)()
+    pi = ctypes.cast(i32, ctypes.c_void_p)
+    E = _abi.SFM_EINVAL
+
+    def motion_dev(ctx=fake, pts=pi, npts=pi, nh=i32, P=1, nmax=8, iters=10, K=d, base=d, op=pi, on=pi, oi=pi,
+                   oR=d, ot=d):
+        return L.sfm_ransac_camera_motion_dev(ctx, pts, npts, nh, P, nmax, iters, ctypes.c_double(1.0), K, base, op,
+                                              on, oi, oR, ot, None)
+
+    for kw in ({"ctx": None}, {"pts": None}, {"npts": None}, {"nh": None}, {"K": None}, {"base": None},
+               {"op": None}, {"on": None}, {"oi": None}, {"oR": None}, {"ot": None}, {"P": 0}, {"P": -1},
+               {"nmax": 0}, {"nmax": -5}, {"iters": -1}):
+        assert motion_dev(**kw) == E, kw
+
+    def motion(ctx=fake, p1=i64, p2=i64, n=8, K1=d, K2=d, Rb=d, Tb=d, iters=10, R=d, t=d, nout=i64):
+        return L.sfm_ransac_camera_motion(ctx, p1, p2, n, K1, K2, Rb, Tb, iters, ctypes.c_double(1.0), R, t, i64,
+                                          i64, nout, None)
+
+    for kw in ({"ctx": None}, {"p1": None}, {"p2": None}, {"n": -1}, {"K1": None}, {"K2": None}, {"Rb": None},
+               {"Tb": None}, {"iters": -1}, {"R": None}, {"t": None}, {"nout": None}):
+        assert motion(**kw) == E, kw
+
+    def tri(ctx=fake, x1=pi, x2=pi, N=4, P1=pi, P2=pi, norm=0, X=pi):
+        return L.sfm_triangulate_dev(ctx, x1, x2, N, P1, P2, norm, X, None)
+
+    for kw in ({"ctx": None}, {"x1": None}, {"x2": None}, {"N": -1}, {"P1": None}, {"P2": None}, {"norm": 2},
+               {"norm": -1}, {"X": None}):
+        assert tri(**kw) == E, kw
+    assert L.sfm_debug_pose_candidates(None, i32, 0) == E
+    assert L.sfm_debug_pose_candidates(fake, None, 0) == E
+    assert L.sfm_debug_pose_candidates(fake, i32, -1) == E
