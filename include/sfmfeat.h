@@ -223,6 +223,44 @@ int32_t sfm_ransac_camera_motion(sfm_ctx* ctx, const int64_t* p1, const int64_t*
 int32_t sfm_triangulate_dev(sfm_ctx* ctx, const double* x1, const double* x2, int64_t N, const double* P1,
                             const double* P2, int32_t normalize, double* X, void* stream);
 
+/* ---- the structure stage: what SFMRunner.perform does with the triangulated points ----
+ * Device pointers, float64 unless said otherwise; enqueued on `stream`, not synchronised.
+ * Argument errors (null pointers, negative sizes, S < 1, max_iter < 1) return SFM_EINVAL with a
+ * message in sfm_last_error. */
+
+/* CameraPose.non_linear_triangulation (SFM.py:255-289; Runner.py:209, :279).  The reference's
+ * joint least-squares problem over all 3N coordinates is a sum of per-point terms, so each
+ * point is refined on its own: Levenberg-Marquardt on the four residuals of SFM.py:262-273
+ * with the analytic Jacobian, lambda from 1e-3, / 10 (floor 1e-12) after an accepted step
+ * (strictly smaller cost), * 10 after a rejected one; stops at an accepted step with
+ * |d| <= 1e-14 |X|, at lambda > 1e12, or after max_iter iterations (the bindings pass 50).
+ * X0, X [N][3] (X may be X0), x1, x2 [N][2], P [S][2][12]: S pairs of row-major 3 x 4
+ * projection matrices (P1, P2); seg [N] int32 picks each point's pair (values are clamped to
+ * [0, S); NULL: every point uses pair 0).  cost [N]: the final sum of squared residuals;
+ * iters [N] int32: accepted steps in bits 0-23, status in bits 24-31 (0 converged by step
+ * size, 1 lambda > 1e12, 2 the initial cost was not finite and the point is returned
+ * unchanged, 3 max_iter ran). */
+int32_t sfm_refine_points_dev(sfm_ctx* ctx, const double* X0, const double* x1, const double* x2, int64_t N,
+                              const double* P, int32_t S, const int32_t* seg, int32_t max_iter, double* X,
+                              double* cost, int32_t* iters, void* stream);
+
+/* Util.print_reprojection_error (Util.py:65-82; Runner.py:211, :282): err [N][2] the two
+ * norms of Util.py:76-77 per point, *mean (device) the mean over points of (e1 + e2) / 2
+ * (Util.py:81), summed in a fixed order (the same bits every run).  P1, P2 [12].  N == 0
+ * writes NaN to *mean, numpy's mean of an empty list. */
+int32_t sfm_reprojection_error_dev(sfm_ctx* ctx, const double* X, const double* x1, const double* x2, int64_t N,
+                                   const double* P1, const double* P2, double* err, double* mean, void* stream);
+
+/* The 2D -> 3D association loop of Runner.py:241-250: for each query qry[q] (prev_frame_2d,
+ * [nq][2] int32) the first nearest target (points_2D_from_prev_frame, tgt [m][2] int32) by the
+ * exact int64 squared distance — np.argmin of the float64 norms — kept iff
+ * sqrt((double)d2) < threshold (Runner.py:245).  The kept (target index, query index) pairs go
+ * to out_tgt / out_qry ([nq] int32 each) in query order, their number to *out_n (device).
+ * Coordinates within +-2^30.  m == 0 returns SFM_EINVAL: the reference fails there too
+ * (np.argmin of an empty sequence). */
+int32_t sfm_link_points_dev(sfm_ctx* ctx, const int32_t* tgt, int32_t m, const int32_t* qry, int32_t nq,
+                            double threshold, int32_t* out_tgt, int32_t* out_qry, int32_t* out_n, void* stream);
+
 /* sfm_ingest_rgb for B frames: rgb [B][H][W][3] uint8 -> gray [B][H2][W2] float32. */
 int32_t sfm_ingest_rgb_dev(sfm_ctx* ctx, const uint8_t* rgb, int32_t B, int32_t H, int32_t W,
                            int32_t H2, int32_t W2, float* gray, void* stream);

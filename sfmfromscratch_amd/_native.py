@@ -60,6 +60,11 @@ SIGNATURES = {
                                                   _i32p]),
     "sfm_triangulate_dev": (ctypes.c_int32, [_vp, _vp, _vp, ctypes.c_int64, _vp, _vp, ctypes.c_int32, _vp, _vp]),
     "sfm_debug_pose_candidates": (ctypes.c_int32, [_vp, _i32p, ctypes.c_int64]),
+    "sfm_refine_points_dev": (ctypes.c_int32, [_vp, _vp, _vp, _vp, ctypes.c_int64, _vp, ctypes.c_int32, _vp,
+                                               ctypes.c_int32, _vp, _vp, _vp, _vp]),
+    "sfm_reprojection_error_dev": (ctypes.c_int32, [_vp, _vp, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp]),
+    "sfm_link_points_dev": (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, _vp, ctypes.c_int32, ctypes.c_double, _vp,
+                                             _vp, _vp, _vp]),
     "sfm_ingest_rgb_dev": (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                             ctypes.c_int32, ctypes.c_int32, _vp, _vp]),
     "sfm_extract_batch_dev": (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp,

@@ -5,6 +5,7 @@
 //   api_extract.hip  c->ex     (pyramid .. descriptors; layout in extract_layout.h)
 //   api_match.hip    c->match  (operands + their owner record, per-pair buffers)
 //   api_stage1.hip   c->ingest, c->ransac, c->pose
+//   api_structure.hip c->structure (the link step's per-query and per-workgroup buffers)
 //   api_profile.hip  c->prof   (stage events, Harris spans, the sfm_debug_* reads)
 #pragma once
 
@@ -157,6 +158,11 @@ struct PoseWs {
   int64_t last_entries = 0;  // P * iters of the last call (sfm_debug_pose_candidates)
 };
 
+// Structure (sfm_link_points_dev): each query's kept target or -1, kept queries per workgroup
+struct StructWs {
+  DevBuf best, block_kept;
+};
+
 struct sfm_ctx {
   CtxStreams s;  // (first: outlives the workspaces below)
   int device = 0;
@@ -175,6 +181,7 @@ struct sfm_ctx {
   IngestWs ingest;
   RansacWs ransac;
   PoseWs pose;
+  StructWs structure;
   // the workspaces free their buffers after this body, the streams and events go last
   ~sfm_ctx() {
     (void)hipSetDevice(device);

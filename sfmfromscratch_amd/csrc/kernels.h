@@ -226,6 +226,31 @@ void launch_pose_gather(const int32_t* out_iter, const double* cand, const int32
 void launch_triangulate(const double* x1, const double* x2, int64_t N, const double* P1, const double* P2,
                         bool normalize, double* scratch30, double* X, hipStream_t st);
 
+// refine.hip: the structure stage.  launch_refine_points:
+// CameraPose.non_linear_triangulation (SFM.py:255-289) as one Levenberg-Marquardt per point;
+// X0, X [N][3], x1, x2 [N][2], P [S][2][12] camera pairs, seg [N] (nullptr: pair 0; clamped to
+// [0, S)), cost [N] the final sum of squared residuals, iters [N] accepted steps | status <<
+// kRefineStatusShift.  X may be X0.
+constexpr int kRefineStatusShift = 24;
+constexpr int kRefineConverged = 0;  // an accepted step with |d| <= 1e-14 |X|
+constexpr int kRefineLambda = 1;     // lambda grew beyond 1e12
+constexpr int kRefineNonFinite = 2;  // initial cost not finite: the point is returned unchanged
+constexpr int kRefineMaxIter = 3;    // max_iter iterations ran
+void launch_refine_points(const double* X0, const double* x1, const double* x2, int64_t N, const double* P, int S,
+                          const int32_t* seg, int max_iter, double* X, double* cost, int32_t* iters,
+                          hipStream_t st);
+// Util.print_reprojection_error (Util.py:65-82): err [N][2] and the mean of (e1 + e2) / 2 (NaN
+// for N == 0), the same bits every run
+void launch_reproj_error(const double* X, const double* x1, const double* x2, int64_t N, const double* P1,
+                         const double* P2, double* err, double* mean, hipStream_t st);
+// the 2D -> 3D association of Runner.py:241-250: tgt [m][2], qry [nq][2] int32 (|coordinate| <=
+// 2^30); out_tgt / out_qry [nq]: the kept (first nearest target, query) pairs in query order,
+// out_n their number; best [nq] and block_kept [link_blocks(nq)] are workspace
+constexpr int kLinkThreads = 256;
+int link_blocks(int nq);
+void launch_link_points(const int32_t* tgt, int m, const int32_t* qry, int nq, double threshold, int32_t* best,
+                        int32_t* block_kept, int32_t* out_tgt, int32_t* out_qry, int32_t* out_n, hipStream_t st);
+
 // ingest.hip: PIL BICUBIC resize of [B][H][W][3] u8 RGB to H2 x W2 + /255 + _rgb2gray
 // (Runner.py:33-46) -> [B][H2][W2] float32; tmp holds [B][H][W2][3] u8.  Tables from
 // build_resample_table (host, Pillow's double-precision taps in 22-bit fixed point).
