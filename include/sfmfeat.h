@@ -261,6 +261,41 @@ int32_t sfm_reprojection_error_dev(sfm_ctx* ctx, const double* X, const double* 
 int32_t sfm_link_points_dev(sfm_ctx* ctx, const int32_t* tgt, int32_t m, const int32_t* qry, int32_t nq,
                             double threshold, int32_t* out_tgt, int32_t* out_qry, int32_t* out_n, void* stream);
 
+/* SFMRunner.add_points with is_new_point / find_existing_point (Runner.py:361-385; called at
+ * :217, :269, :280): the global registry of 3-D points.  reg_xyz [reg_capacity][3] float64 and
+ * *reg_count (int32) are caller-owned device memory holding the registry and its size; the
+ * caller guarantees reg_capacity >= *reg_count + n (the sum of the n of all calls so far bounds
+ * the count without reading the device).  pts [n][3] are processed in order, as the
+ * reference's loop: with d_j = sqrt((dx*dx + dy*dy) + dz*dz) (float64, no fused multiply-add,
+ * correctly rounded sqrt) against every registered point, including those appended earlier
+ * in this call, a point with no registered point or min_j d_j >= threshold is appended and
+ * takes the new last index; otherwise it takes the first index of the smallest distance.
+ * out_index [n] int32 receives that index, out_is_new [n] int32 1 where the point was
+ * appended; reg_xyz gains the new coordinates (copied bit for bit) and *reg_count their
+ * number.  The reference's threshold is 1e-6.  Finite coordinates are the caller's contract
+ * (a NaN compares false everywhere the reference's min / argmin would propagate it).
+ * SFM_EINVAL: a negative size, a null pointer, threshold <= 0 (or NaN), reg_capacity < n,
+ * reg_capacity > 2^30 or n > 2^24; n == 0 does nothing.  Calls on one registry must be ordered
+ * (one stream, or events); the context's workspace serves one call at a time. */
+int32_t sfm_registry_add_dev(sfm_ctx* ctx, double* reg_xyz, int32_t* reg_count, int32_t reg_capacity,
+                             const double* pts, int32_t n, double threshold, int32_t* out_index,
+                             int32_t* out_is_new, void* stream);
+
+/* SFMRunner.total_reprojection_error (Runner.py:311-334, printed before and after bundle
+ * adjustment) over the M observations of prepare_for_ba (Runner.py:387-401): for observation o,
+ * R = Rodrigues(camera_params[cam_idx[o]][0:3]) (theta = |r|; identity for theta < DBL_EPSILON,
+ * else cos(theta) I + (1 - cos(theta)) k k^T + sin(theta) [k]x with k = r / theta),
+ * q = K[cam_idx[o]] (R X[pt_idx[o]] + camera_params[cam_idx[o]][3:6]) and
+ * err[o] = |q[:2] / q[2] - obs[o]|; *mean (device) is their mean, summed in a fixed order (the
+ * same bits every run; NaN for M == 0, where the reference divides by zero).  cam_idx, pt_idx
+ * [M] int32, obs [M][2], camera_params [n_cam][6], K [n_cam][9] row-major, X [n_pts][3].
+ * Indices within their tables are the caller's contract (values are clamped, like seg in
+ * sfm_refine_points_dev).  SFM_EINVAL: M < 0, a null pointer, M > 0 with n_cam or n_pts < 1. */
+int32_t sfm_total_reprojection_error_dev(sfm_ctx* ctx, const int32_t* cam_idx, const int32_t* pt_idx,
+                                         const double* obs, int64_t M, const double* camera_params, int32_t n_cam,
+                                         const double* K, const double* X, int32_t n_pts, double* err, double* mean,
+                                         void* stream);
+
 /* sfm_ingest_rgb for B frames: rgb [B][H][W][3] uint8 -> gray [B][H2][W2] float32. */
 int32_t sfm_ingest_rgb_dev(sfm_ctx* ctx, const uint8_t* rgb, int32_t B, int32_t H, int32_t W,
                            int32_t H2, int32_t W2, float* gray, void* stream);

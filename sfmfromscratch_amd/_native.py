@@ -65,6 +65,10 @@ SIGNATURES = {
     "sfm_reprojection_error_dev": (ctypes.c_int32, [_vp, _vp, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp]),
     "sfm_link_points_dev": (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, _vp, ctypes.c_int32, ctypes.c_double, _vp,
                                              _vp, _vp, _vp]),
+    "sfm_registry_add_dev": (ctypes.c_int32, [_vp, _vp, _vp, ctypes.c_int32, _vp, ctypes.c_int32, ctypes.c_double,
+                                              _vp, _vp, _vp]),
+    "sfm_total_reprojection_error_dev": (ctypes.c_int32, [_vp, _vp, _vp, _vp, ctypes.c_int64, _vp, ctypes.c_int32,
+                                                          _vp, _vp, ctypes.c_int32, _vp, _vp, _vp]),
     "sfm_ingest_rgb_dev": (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                             ctypes.c_int32, ctypes.c_int32, _vp, _vp]),
     "sfm_extract_batch_dev": (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp,

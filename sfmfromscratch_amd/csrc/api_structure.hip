@@ -1,5 +1,7 @@
 // api_structure.hip — the structure stage (refine.hip): refinement, reprojection error and the
-// 2D -> 3D association of the triangulated points (workspace c->structure).  Every call is
+// 2D -> 3D association of the triangulated points (workspace c->structure), then what follows
+// them (registry.hip): the global point registry and the total reprojection error (workspace
+// c->registry, the table itself being the caller's).  Every call is
 // enqueued on the caller's stream and checks its arguments before touching the device.
 #include "ctx.h"
 
@@ -62,6 +64,57 @@ int32_t sfm_link_points_dev(sfm_ctx* c, const int32_t* tgt, int32_t m, const int
   if ((rc = ensure(c, w.block_kept, (size_t)link_blocks(nq) * 4))) return rc;
   launch_link_points(tgt, m, qry, nq, threshold, as<int32_t>(w.best), as<int32_t>(w.block_kept), out_tgt, out_qry,
                      out_n, st);
+  HIPCHK(c, hipGetLastError());
+  return SFM_OK;
+}
+
+int32_t sfm_registry_add_dev(sfm_ctx* c, double* reg_xyz, int32_t* reg_count, int32_t reg_capacity,
+                             const double* pts, int32_t n, double threshold, int32_t* out_index,
+                             int32_t* out_is_new, void* stream) {
+  if (!c) return SFM_EINVAL;
+  if (n < 0 || reg_capacity < 0) return set_err(c, SFM_EINVAL, "sfm_registry_add_dev: a size is negative");
+  if (!(threshold > 0.0)) return set_err(c, SFM_EINVAL, "sfm_registry_add_dev: threshold must be positive");
+  if (!reg_xyz || !reg_count) return set_err(c, SFM_EINVAL, "sfm_registry_add_dev: reg_xyz or reg_count is null");
+  if (n > 0 && (!pts || !out_index || !out_is_new))
+    return set_err(c, SFM_EINVAL, "sfm_registry_add_dev: pts, out_index or out_is_new is null");
+  if (reg_capacity < n)
+    return set_err(c, SFM_EINVAL, "sfm_registry_add_dev: reg_capacity < n (capacity >= count + n is required)");
+  if (reg_capacity > (1 << 30) || n > (1 << 24))
+    return set_err(c, SFM_EINVAL, "sfm_registry_add_dev: at most 2^30 registered and 2^24 incoming points");
+  if (n == 0) return SFM_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc, splits_old, splits_self;
+  (void)registry_span(reg_capacity, &splits_old);
+  (void)registry_span(n, &splits_self);
+  RegistryWs& w = c->registry;
+  if ((rc = ensure(c, w.part_d, (size_t)splits_old * n * 8))) return rc;
+  if ((rc = ensure(c, w.part_j, (size_t)splits_old * n * 4))) return rc;
+  if ((rc = ensure(c, w.self_d, (size_t)splits_self * n * 8))) return rc;
+  if ((rc = ensure(c, w.old_d, (size_t)n * 8))) return rc;
+  if ((rc = ensure(c, w.old_j, (size_t)n * 4))) return rc;
+  if ((rc = ensure(c, w.res, (size_t)n * 4))) return rc;
+  if ((rc = ensure(c, w.clist, (size_t)n * 4))) return rc;
+  launch_registry_add(reg_xyz, reg_count, reg_capacity, pts, n, threshold, as<double>(w.part_d),
+                      as<int32_t>(w.part_j), as<double>(w.self_d), as<double>(w.old_d), as<int32_t>(w.old_j),
+                      as<int32_t>(w.res), as<int32_t>(w.clist), out_index, out_is_new, (hipStream_t)stream);
+  HIPCHK(c, hipGetLastError());
+  return SFM_OK;
+}
+
+int32_t sfm_total_reprojection_error_dev(sfm_ctx* c, const int32_t* cam_idx, const int32_t* pt_idx,
+                                         const double* obs, int64_t M, const double* camera_params, int32_t n_cam,
+                                         const double* K, const double* X, int32_t n_pts, double* err, double* mean,
+                                         void* stream) {
+  if (!c) return SFM_EINVAL;
+  if (M < 0) return set_err(c, SFM_EINVAL, "sfm_total_reprojection_error_dev: M is negative");
+  if (!mean) return set_err(c, SFM_EINVAL, "sfm_total_reprojection_error_dev: mean is null");
+  if (M > 0 && (!cam_idx || !pt_idx || !obs || !camera_params || !K || !X || !err))
+    return set_err(c, SFM_EINVAL, "sfm_total_reprojection_error_dev: an input or output pointer is null");
+  if (M > 0 && (n_cam < 1 || n_pts < 1))
+    return set_err(c, SFM_EINVAL, "sfm_total_reprojection_error_dev: observations without cameras or points");
+  if (M > ((int64_t)1 << 37)) return set_err(c, SFM_EINVAL, "sfm_total_reprojection_error_dev: too many observations");
+  HIPCHK(c, hipSetDevice(c->device));
+  launch_total_reproj(cam_idx, pt_idx, obs, M, camera_params, n_cam, K, X, n_pts, err, mean, (hipStream_t)stream);
   HIPCHK(c, hipGetLastError());
   return SFM_OK;
 }

@@ -5,7 +5,8 @@
 //   api_extract.hip  c->ex     (pyramid .. descriptors; layout in extract_layout.h)
 //   api_match.hip    c->match  (operands + their owner record, per-pair buffers)
 //   api_stage1.hip   c->ingest, c->ransac, c->pose
-//   api_structure.hip c->structure (the link step's per-query and per-workgroup buffers)
+//   api_structure.hip c->structure (the link step's per-query and per-workgroup buffers),
+//                    c->registry  (the point registry's partials and per-point state)
 //   api_profile.hip  c->prof   (stage events, Harris spans, the sfm_debug_* reads)
 #pragma once
 
@@ -163,6 +164,13 @@ struct StructWs {
   DevBuf best, block_kept;
 };
 
+// Registry (sfm_registry_add_dev): per-(point, split) partials against the old registry and
+// against the call's own points, each point's old hit, its resolution and the contested list.
+// The table and its count are the caller's.
+struct RegistryWs {
+  DevBuf part_d, part_j, self_d, old_d, old_j, res, clist;
+};
+
 struct sfm_ctx {
   CtxStreams s;  // (first: outlives the workspaces below)
   int device = 0;
@@ -182,6 +190,7 @@ struct sfm_ctx {
   RansacWs ransac;
   PoseWs pose;
   StructWs structure;
+  RegistryWs registry;
   // the workspaces free their buffers after this body, the streams and events go last
   ~sfm_ctx() {
     (void)hipSetDevice(device);

@@ -251,6 +251,26 @@ int link_blocks(int nq);
 void launch_link_points(const int32_t* tgt, int m, const int32_t* qry, int nq, double threshold, int32_t* best,
                         int32_t* block_kept, int32_t* out_tgt, int32_t* out_qry, int32_t* out_n, hipStream_t st);
 
+// registry.hip: the global 3-D point registry (SFMRunner.add_points, Runner.py:361-385;
+// DESIGN.md §13C).  reg_xyz [capacity][3] and *reg_count are the caller's device memory,
+// pts [n][3]; out_index [n] each point's registry index, out_is_new [n] 1 where it was appended.
+// Workspace: part_d / part_j [splits_old][n], self_d [splits_self][n] (registry_span gives the
+// splits of `capacity` and of n entries), old_d, old_j, res, clist [n].
+constexpr int kRegThreads = 256;     // points per workgroup (one each)
+constexpr int kRegChunk = 256;       // registry entries staged in LDS at a time (24 B each); short, so that a
+                                     // small registry still spreads over many workgroups
+constexpr int kRegMaxSplits = 1024;  // workgroups across the registry (grid.y); longer tables: longer spans
+int registry_span(int entries, int* splits);
+void launch_registry_add(double* reg_xyz, int32_t* reg_count, int capacity, const double* pts, int n, double thr,
+                         double* part_d, int32_t* part_j, double* self_d, double* old_d, int32_t* old_j,
+                         int32_t* res, int32_t* clist, int32_t* out_index, int32_t* out_is_new, hipStream_t st);
+// SFMRunner.total_reprojection_error (Runner.py:311-334): cam_idx, pt_idx [M] int32 (clamped to
+// their tables), obs [M][2], cams [n_cam][6] (Rodrigues vector, t), K [n_cam][9], X [n_pts][3];
+// err [M] and their mean (NaN for M == 0), the same bits every run
+void launch_total_reproj(const int32_t* cam_idx, const int32_t* pt_idx, const double* obs, int64_t M,
+                         const double* cams, int n_cam, const double* K, const double* X, int n_pts, double* err,
+                         double* mean, hipStream_t st);
+
 // ingest.hip: PIL BICUBIC resize of [B][H][W][3] u8 RGB to H2 x W2 + /255 + _rgb2gray
 // (Runner.py:33-46) -> [B][H2][W2] float32; tmp holds [B][H][W2][3] u8.  Tables from
 // build_resample_table (host, Pillow's double-precision taps in 22-bit fixed point).

@@ -15,7 +15,9 @@ Below: the consumer of the pair the filter leaves alone, CameraPose.ransac_camer
 (SFM.py:38-124), and the linear triangulation it is built from (pose.hip).
 At the end: what SFMRunner.perform does with the triangulated points — refinement
 (CameraPose.non_linear_triangulation), the reprojection error and the 2D -> 3D association
-of the next pair (refine.hip).
+of the next pair (refine.hip) — and then with every batch of them: the
+global point registry (SFMRunner.add_points), prepare_for_ba and total_reprojection_error
+(PointRegistry; registry.hip), with a host stand-in for cv2.Rodrigues.
 """
 from __future__ import annotations
 
@@ -499,3 +501,235 @@ def initial_structure(p1, p2, K1, K2, max_iterations, threshold=1.0, device: int
     X = non_linear_triangulation(_triangulate(a, b, A, B, False, device), a, b, A, B)
     mean, _ = _reprojection_dev(X, a, b, A, B, dev)
     return R2, t2, in1, in2, X.cpu().numpy(), float(mean.cpu()[0])
+
+
+# ---------------- the point registry and the BA-input score (registry.hip) ----------------
+
+REGISTRY_THRESHOLD = 1e-6      # is_new_point / find_existing_point's default (Runner.py:373, :380)
+REGISTRY_CHUNK = 256           # registry entries one workgroup stages at a time (kernels.h kRegChunk)
+REGISTRY_MIN_CAPACITY = 1024
+
+
+def rodrigues(a):
+    """Host numpy drop-in for the cv2.Rodrigues calls of Runner.py:213, :285 and
+    PoseEstimator.py:68: a 3-vector gives (R [3, 3], None) with theta = |r|, R = I for
+    theta < DBL_EPSILON, else cos(theta) I + (1 - cos(theta)) k k^T + sin(theta) [k]x, k = r / theta;
+    a 3 x 3 rotation gives (r [3, 1], None): the axis from the antisymmetric part, the angle
+    from atan2(sin, cos); beyond theta = pi / 2, where the antisymmetric part fades, the axis
+    comes from the symmetric part (R_ii = c + (1 - c) k_i^2, the signs from the off-diagonal
+    sums and what is left of the antisymmetric part), so theta = pi is an ordinary case.  Parity with OpenCV is not pinned
+    (DESIGN.md §13C); no Jacobian is returned."""
+    a = np.asarray(a, np.float64)
+    if a.size == 3:
+        r = a.reshape(3)
+        th = np.sqrt((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2])
+        if th < np.finfo(np.float64).eps:
+            return np.eye(3), None
+        k = r / th
+        c, s = np.cos(th), np.sin(th)
+        Kx = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
+        return c * np.eye(3) + (1.0 - c) * np.outer(k, k) + s * Kx, None
+    if a.shape != (3, 3):
+        raise ValueError("rodrigues: a 3-vector or a 3 x 3 matrix")
+    v = np.array([a[2, 1] - a[1, 2], a[0, 2] - a[2, 0], a[1, 0] - a[0, 1]]) / 2.0
+    s = np.sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2])
+    c = (a[0, 0] + a[1, 1] + a[2, 2] - 1.0) / 2.0
+    th = np.arctan2(s, c)
+    if c >= 0:  # theta <= pi / 2: the antisymmetric part is sin(theta) k
+        return (v.copy() if s == 0 else v * (th / s)).reshape(3, 1), None
+    k2 = np.maximum((np.diag(a) - c) / (1.0 - c), 0.0)
+    i = int(np.argmax(k2))
+    k = np.zeros(3)
+    k[i] = -np.sqrt(k2[i]) if v[i] < 0 else np.sqrt(k2[i])
+    for j in range(3):
+        if j != i:
+            k[j] = (a[i, j] + a[j, i]) / 2.0 / ((1.0 - c) * k[i])
+    k = k / np.sqrt((k[0] * k[0] + k[1] * k[1]) + k[2] * k[2])
+    return (k * th).reshape(3, 1), None
+
+
+def _i32_dev(a, n, dev, what):
+    import torch
+    if isinstance(a, torch.Tensor):
+        t = a
+    else:
+        t = torch.from_numpy(np.ascontiguousarray(np.asarray(a).reshape(-1), np.int64))
+    if t.numel() < n:
+        raise ValueError(f"{what} has fewer than {n} entries")
+    return t.reshape(-1)[:n].to(device=dev, dtype=torch.int32).contiguous()
+
+
+class PointRegistry:
+    """The global 3-D point list of SFMRunner (global_points_3D, global_points_2D,
+    frame_indices, point_indices; Runner.py:361-401) kept on the device.
+
+    add_points is SFMRunner.add_points: the points are processed in order; one that lies at
+    least `threshold` (float64 norm) from every registered point — those appended earlier in the
+    same call included — is appended, any other takes the first index of the smallest distance.
+    Indices and registry equal the reference's bit for bit.  Nothing synchronises until a
+    property is read: the table grows geometrically from the number of points passed in so
+    far, an upper bound of the registered count that needs no device read."""
+
+    def __init__(self, device: int = 0, threshold: float = REGISTRY_THRESHOLD):
+        import torch
+        if not threshold > 0:
+            raise ValueError("PointRegistry: threshold must be positive")
+        self.threshold = float(threshold)
+        self._dev = torch.device("cuda", device)
+        self._table = torch.empty((REGISTRY_MIN_CAPACITY, 3), dtype=torch.float64, device=self._dev)
+        self._count = torch.zeros(1, dtype=torch.int32, device=self._dev)
+        self._bound = 0           # points passed in so far >= the registered count
+        self._idx, self._new, self._frames, self._p2 = [], [], [], []
+
+    def _reserve(self, n):
+        import torch
+        need = self._bound + n
+        cap = int(self._table.shape[0])
+        if need <= cap:
+            return
+        grown = torch.empty((max(2 * cap, need), 3), dtype=torch.float64, device=self._dev)
+        grown[:self._bound].copy_(self._table[:self._bound])
+        self._table = grown
+
+    def add_points(self, points_3d, points_2d, frame_idx, info=None):
+        """SFMRunner.add_points(points_3d, points_2d, frame_idx).  numpy arrays or device
+        tensors; points_3d [n, 3], points_2d [n, 2] (an empty array of any shape is no points,
+        as the reference's np.array([]) of a frame without links).  ValueError on a shape
+        mismatch and on non-finite numpy points_3d (for device tensors finite coordinates
+        are the caller's contract).  info (optional dict) receives the call's "point_indices"
+        and "is_new" as device tensors."""
+        import torch
+        s3, s2 = _shape_of(points_3d), _shape_of(points_2d)
+        if int(np.prod(s3)) == 0 and int(np.prod(s2)) == 0:
+            if info is not None:
+                e = torch.empty(0, dtype=torch.int32, device=self._dev)
+                info.update(point_indices=e, is_new=e.clone())
+            return
+        if len(s3) != 2 or s3[1] != 3:
+            raise ValueError("add_points: points_3d must be [n, 3]")
+        n = s3[0]
+        if s2 != (n, 2):
+            raise ValueError("add_points: points_2d must be [n, 2] with points_3d's n")
+        if not _is_dev(points_3d) and not np.isfinite(np.asarray(points_3d, np.float64)).all():
+            raise ValueError("add_points: points_3d must be finite")
+        with torch.cuda.device(self._dev):
+            pts = _f64_dev(points_3d, (n, 3), self._dev)
+            self._reserve(n)
+            idx = torch.empty(n, dtype=torch.int32, device=self._dev)
+            new = torch.empty(n, dtype=torch.int32, device=self._dev)
+            ctx, stream = _structure_ctx(self._dev)
+            check(ctx.lib.sfm_registry_add_dev(ctx.handle, self._table.data_ptr(), self._count.data_ptr(),
+                                               int(self._table.shape[0]), pts.data_ptr(), n, self.threshold,
+                                               idx.data_ptr(), new.data_ptr(), stream or None), ctx.handle)
+            self._bound += n
+            self._idx.append(idx)
+            self._new.append(new)
+            self._frames.append(torch.full((n,), int(frame_idx), dtype=torch.int64, device=self._dev))
+            self._p2.append(points_2d if _is_dev(points_2d)
+                            else torch.from_numpy(np.ascontiguousarray(points_2d)).to(self._dev))
+        if info is not None:
+            info.update(point_indices=idx, is_new=new)
+
+    def __len__(self):
+        return int(self._count.cpu()[0])
+
+    @staticmethod
+    def _cat(chunks, empty):
+        return np.concatenate([c.cpu().numpy() for c in chunks]) if chunks else empty
+
+    @property
+    def point_indices(self):
+        return self._cat(self._idx, np.empty(0, np.int32)).astype(np.int64)
+
+    @property
+    def frame_indices(self):
+        return self._cat(self._frames, np.empty(0, np.int64))
+
+    @property
+    def points_3d(self):
+        return self._table[:len(self)].cpu().numpy()
+
+    @property
+    def points_2d(self):
+        return self._cat(self._p2, np.empty((0, 2)))
+
+    @property
+    def points_3d_device(self):
+        """The registered points as a device tensor view (valid until the next add_points)."""
+        return self._table[:len(self)]
+
+    def prepare_for_ba(self, global_poses, global_K):
+        """SFMRunner.prepare_for_ba (Runner.py:387-401) with the poses [(Rodrigues vector, t), ...]
+        and intrinsics perform collects: (num_cameras, num_points, camera_indices, point_indices,
+        points_2D, camera_params, points_3D, K_list)."""
+        frames = self.frame_indices
+        camera_params = np.array([np.hstack((np.asarray(p[0]).flatten(), np.asarray(p[1]).flatten()))
+                                  for p in global_poses])
+        p3 = self.points_3d
+        return (len(set(frames.tolist())), len(p3), frames, self.point_indices, self.points_2d, camera_params,
+                p3, np.array(global_K))
+
+    def total_reprojection_error(self, num_points, camera_indices, point_indices, points_2D, camera_params,
+                                 points_3D, K_list, info=None):
+        """SFMRunner.total_reprojection_error (Runner.py:311-334): the mean over the first
+        num_points observations (the reference's bound, although prepare_for_ba's num_points
+        counts 3-D points) of |pi(K (R X + t)) - observation|, on the device, summed in a fixed
+        order.  Arrays are numpy or device tensors; numpy indices outside their tables raise
+        IndexError (device indices are the caller's contract).  info (optional dict) receives
+        "errors" [num_points] (numpy)."""
+        import torch
+        M = int(num_points)
+        if M < 0:
+            raise ValueError("total_reprojection_error: num_points is negative")
+        dev = self._dev
+        with torch.cuda.device(dev):
+            cams = _f64_dev(camera_params, (-1, 6), dev)
+            K = _f64_dev(K_list, (-1, 3, 3), dev)
+            X = _f64_dev(points_3D, (-1, 3), dev)
+            obs = _f64_dev(points_2D, (-1, 2), dev)
+            n_cam, n_pts = int(cams.shape[0]), int(X.shape[0])
+            if int(K.shape[0]) < n_cam:
+                raise ValueError("total_reprojection_error: K_list has fewer entries than camera_params")
+            if int(obs.shape[0]) < M:
+                raise ValueError("total_reprojection_error: fewer than num_points observations")
+            for a, hi, what in ((camera_indices, n_cam, "camera"), (point_indices, n_pts, "point")):
+                if not _is_dev(a) and M:
+                    h = np.asarray(a).reshape(-1)[:M]
+                    if h.size and (h.min() < 0 or h.max() >= hi):
+                        raise IndexError(f"total_reprojection_error: a {what} index is outside its table")
+            ci = _i32_dev(camera_indices, M, dev, "camera_indices")
+            pi = _i32_dev(point_indices, M, dev, "point_indices")
+            err = torch.empty(max(M, 1), dtype=torch.float64, device=dev)
+            mean = torch.empty(1, dtype=torch.float64, device=dev)
+            ctx, stream = _structure_ctx(dev)
+            check(ctx.lib.sfm_total_reprojection_error_dev(
+                ctx.handle, ci.data_ptr(), pi.data_ptr(), obs.data_ptr(), M, cams.data_ptr(), n_cam, K.data_ptr(),
+                X.data_ptr(), n_pts, err.data_ptr(), mean.data_ptr(), stream or None), ctx.handle)
+            if info is not None:
+                info["errors"] = err[:M].cpu().numpy()
+            return float(mean.cpu()[0])
+
+    def save(self, path):
+        """SFMRunner.save_data's file (Runner.py:357-359): p3d, frame_idx, pt_idx."""
+        np.savez(path, p3d=self.points_3d, frame_idx=self.frame_indices, pt_idx=self.point_indices)
+
+    @classmethod
+    def load(cls, path, device: int = 0, threshold: float = REGISTRY_THRESHOLD):
+        """A registry holding a saved model's points and indices (the file has no 2-D observations:
+        points_2d starts empty)."""
+        import torch
+        z = np.load(path)
+        p3 = np.ascontiguousarray(z["p3d"], np.float64).reshape(-1, 3)
+        r = cls(device, threshold)
+        m = len(p3)
+        r._reserve(m)
+        r._bound = m
+        if m:
+            r._table[:m].copy_(torch.from_numpy(p3))
+        r._count.fill_(m)
+        pt = np.ascontiguousarray(z["pt_idx"], np.int64).reshape(-1)
+        fr = np.ascontiguousarray(z["frame_idx"], np.int64).reshape(-1)
+        if len(pt):
+            r._idx.append(torch.from_numpy(pt.astype(np.int32)).to(r._dev))
+            r._frames.append(torch.from_numpy(fr).to(r._dev))
+        return r
