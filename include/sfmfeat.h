@@ -168,6 +168,11 @@ int32_t sfm_ransac_find_inliers(sfm_ctx* ctx, const int64_t* p1, const int64_t* 
  * iterations after np.random.seed(seed) (numpy legacy MT19937 + Fisher-Yates):
  * out [iters][8] int32.  Host-only. */
 int32_t sfm_ransac_sample_indices(int32_t n, int32_t iters, uint32_t seed, int32_t* out);
+/* The same stream with `size` indices kept per iteration, np.random.choice(n, size,
+ * replace=False): out [iters][size] int32; size 8 is sfm_ransac_sample_indices.  numpy's legacy
+ * choice without replacement is permutation(n)[:size], so the draws consumed per iteration do
+ * not depend on size.  SFM_EINVAL: size < 1, n < size, iters < 0, out null.  Host-only. */
+int32_t sfm_ransac_sample_indices_k(int32_t n, int32_t iters, uint32_t seed, int32_t size, int32_t* out);
 
 /* ---------------- device-resident batch API (throughput path) ----------------
  * All pointers are device pointers on the context's device; `stream` is the
@@ -295,6 +300,50 @@ int32_t sfm_total_reprojection_error_dev(sfm_ctx* ctx, const int32_t* cam_idx, c
                                          const double* obs, int64_t M, const double* camera_params, int32_t n_cam,
                                          const double* K, const double* X, int32_t n_pts, double* err, double* mean,
                                          void* stream);
+
+/* The pose of a frame from its 2D-3D links (Runner.py:257-262, PoseEstimator.PnPRansac): the
+ * library's own rule in the spirit of cv2.solvePnPRansac(reprojectionError = 8,
+ * iterationsCount = iters, flags = SOLVEPNP_ITERATIVE).  Parity with OpenCV is NOT pinned
+ * (DESIGN.md §13D); the rule is pinned to a numpy restatement, planted poses and scipy.
+ * X [n][3] world points, x [n][2] pixels, K [9] row-major upper triangular (skew allowed); all
+ * float64 on the device.
+ *  1. Sample s = the first 6 indices of sfm_ransac_sample_indices(n, iters, 5)[s] (for n < 8:
+ *     sfm_ransac_sample_indices_k with size 6).  n < 6: no pose.
+ *  2. Hypothesis: image points through K^-1; the six world points as Y = s (X - c), c their
+ *     centroid, s = sqrt(3) / mean |X - c|; DLT rows [Yh, 0, -u Yh], [0, Yh, -v Yh] per point,
+ *     the first 11 of the 12; the null vector with last component 1 by Gaussian elimination
+ *     with partial pivoting; P negated when det P[:, :3] < 0; R = the polar factor of
+ *     M = P[:, :3], sigma = M's mean singular value, t = (P[:, 3] / sigma - s R c) / s.  A
+ *     zero pivot or a non-finite result gives a NaN hypothesis.
+ *  3. Count: points with depth (R X + t)[2] > 0 and |pi(K (R X + t)) - x| < threshold.
+ *  4. The first sample with the strictly largest count wins; all counts 0 (or iters == 0): no
+ *     pose.  out_inliers [n] receives the winner's inlier indices in ascending order, *out_n
+ *     their number (0: no pose; -1: n < 6), *out_iter the winner (-1: none).
+ *  5. Levenberg-Marquardt over the winner's inliers on (d omega, d t), R <- exp([d omega]x) R,
+ *     t <- t + d t: residuals pi(K (R X + t)) - x, (J^T J + lambda diag J^T J) d = -J^T r by
+ *     Cholesky, lambda from 1e-3; a step is accepted iff the cost is strictly smaller, then
+ *     lambda <- max(lambda / 10, 1e-12), else lambda <- 10 lambda.  Status as
+ *     sfm_refine_points_dev: 0 an accepted step with |d| <= 1e-14 max(1, |t|), 1 lambda > 1e12,
+ *     3 max_refine_iter iterations, 2 non-finite start cost (pose unchanged).  The inliers
+ *     are not re-scored.
+ * Outputs (device): R [9] row-major, t [3] (NaN without a pose), out_status [4] = found (0 / 1),
+ * LM status (-1 without a pose), accepted steps, iterations run; out_cost [2] = the sum of
+ * squared residuals at the winning hypothesis and at the returned pose; out_counts [iters]
+ * (optional) every sample's count.  Sums run in a fixed order: the same bits every run.
+ * Enqueued on `stream`; the call synchronises only when the context first uploads the sample
+ * stream of (n, iters).  One call at a time per context.  SFM_EINVAL: a null pointer,
+ * n < 0, iters < 0, threshold not positive, max_refine_iter outside [1, 2^24). */
+int32_t sfm_pnp_ransac_dev(sfm_ctx* ctx, const double* X, const double* x, const double* K, int32_t n,
+                           int32_t iters, double threshold, int32_t max_refine_iter, double* R, double* t,
+                           int32_t* out_inliers, int32_t* out_n, int32_t* out_iter, int32_t* out_status,
+                           double* out_cost, int32_t* out_counts, void* stream);
+/* PoseEstimator.PnP (no RANSAC): the DLT of step 2 over all n >= 6 points (normalised over all
+ * of them; the eigenvector of the smallest eigenvalue of the 12 x 12 A^T A by cyclic Jacobi),
+ * the same P -> (R, t), then step 5 over all points.  Outputs as above (found 0 for n < 6 or a
+ * non-finite DLT pose). */
+int32_t sfm_pnp_dev(sfm_ctx* ctx, const double* X, const double* x, const double* K, int32_t n,
+                    int32_t max_refine_iter, double* R, double* t, int32_t* out_status, double* out_cost,
+                    void* stream);
 
 /* sfm_ingest_rgb for B frames: rgb [B][H][W][3] uint8 -> gray [B][H2][W2] float32. */
 int32_t sfm_ingest_rgb_dev(sfm_ctx* ctx, const uint8_t* rgb, int32_t B, int32_t H, int32_t W,

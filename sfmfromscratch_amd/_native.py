@@ -50,6 +50,8 @@ SIGNATURES = {
     "sfm_ransac_find_inliers": (ctypes.c_int32, [_vp, _i64p, _i64p, ctypes.c_int64, ctypes.c_int32, ctypes.c_double,
                                                  _i64p, _i64p, _i64p, _i32p]),
     "sfm_ransac_sample_indices": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, ctypes.c_uint32, _i32p]),
+    "sfm_ransac_sample_indices_k": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, ctypes.c_uint32, ctypes.c_int32,
+                                                     _i32p]),
     "sfm_ransac_find_inliers_dev": (ctypes.c_int32, [_vp, _vp, _vp, _i32p, ctypes.c_int32, ctypes.c_int32,
                                                      ctypes.c_int32, ctypes.c_double, _vp, _vp, _vp, _vp]),
     "sfm_ransac_camera_motion_dev": (ctypes.c_int32, [_vp, _vp, _vp, _i32p, ctypes.c_int32, ctypes.c_int32,
@@ -69,6 +71,9 @@ SIGNATURES = {
                                               _vp, _vp, _vp]),
     "sfm_total_reprojection_error_dev": (ctypes.c_int32, [_vp, _vp, _vp, _vp, ctypes.c_int64, _vp, ctypes.c_int32,
                                                           _vp, _vp, ctypes.c_int32, _vp, _vp, _vp]),
+    "sfm_pnp_ransac_dev": (ctypes.c_int32, [_vp, _vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
+                                            ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sfm_pnp_dev": (ctypes.c_int32, [_vp, _vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "sfm_ingest_rgb_dev": (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                             ctypes.c_int32, ctypes.c_int32, _vp, _vp]),
     "sfm_extract_batch_dev": (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp,

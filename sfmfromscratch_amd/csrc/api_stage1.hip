@@ -226,6 +226,11 @@ int ransac_host_pair(sfm_ctx* c, const int64_t* p1, const int64_t* p2, int64_t n
 
 }  // namespace
 
+const std::vector<int32_t>& ransac_stream(sfm_ctx* c, int n, int iters) {
+  ransac_prefetch_streams(c, {n}, iters);
+  return *ransac_cached(c, n, iters);
+}
+
 extern "C" {
 
 int32_t sfm_resize_dims(int32_t H, int32_t W, double scale, int32_t* H2, int32_t* W2) {
@@ -266,6 +271,12 @@ int32_t sfm_ingest_rgb(sfm_ctx* c, const uint8_t* rgb, int32_t H, int32_t W, int
 int32_t sfm_ransac_sample_indices(int32_t n, int32_t iters, uint32_t seed, int32_t* out) {
   if (n < 8 || iters < 0 || !out) return SFM_EINVAL;
   ransac_sample_indices(n, iters, seed, out);
+  return SFM_OK;
+}
+
+int32_t sfm_ransac_sample_indices_k(int32_t n, int32_t iters, uint32_t seed, int32_t size, int32_t* out) {
+  if (size < 1 || n < size || iters < 0 || !out) return SFM_EINVAL;
+  ransac_sample_indices_k(n, iters, seed, size, out);
   return SFM_OK;
 }
 

@@ -7,6 +7,8 @@
 //   api_stage1.hip   c->ingest, c->ransac, c->pose
 //   api_structure.hip c->structure (the link step's per-query and per-workgroup buffers),
 //                    c->registry  (the point registry's partials and per-point state)
+//   api_pnp.hip      c->pnp (sample stream on the device, hypotheses, counts; the host streams
+//                    are c->ransac's cache)
 //   api_profile.hip  c->prof   (stage events, Harris spans, the sfm_debug_* reads)
 #pragma once
 
@@ -171,6 +173,14 @@ struct RegistryWs {
   DevBuf part_d, part_j, self_d, old_d, old_j, res, clist;
 };
 
+// PnP (sfm_pnp_ransac_dev, sfm_pnp_dev): the device copy of one sample stream and the (n,
+// iterations) it belongs to, per-sample hypotheses (R, t) and counts, the start pose of the
+// refinement.  One call at a time per context, like StructWs.
+struct PnpWs {
+  DevBuf idx, hyp, counts, Rt;
+  int idx_n = -1, idx_iters = -1, idx_stride = 0;
+};
+
 struct sfm_ctx {
   CtxStreams s;  // (first: outlives the workspaces below)
   int device = 0;
@@ -191,6 +201,7 @@ struct sfm_ctx {
   PoseWs pose;
   StructWs structure;
   RegistryWs registry;
+  PnpWs pnp;
   // the workspaces free their buffers after this body, the streams and events go last
   ~sfm_ctx() {
     (void)hipSetDevice(device);
@@ -277,6 +288,10 @@ const ExtractSwitches& extract_switches();  // api_extract.hip
 int extract_reserve(sfm_ctx* c, int B, int H, int W);
 int extract_impl(sfm_ctx* c, const float* imgs, int B, int H, int W, int32_t* xy, float* desc, float* conf,
                  int32_t* count, int64_t cap, hipStream_t st);
+
+// api_stage1.hip: the cached [iters][8] sample stream of (n >= 8, iters) (RansacWs::cache; valid
+// until the next call that touches the cache)
+const std::vector<int32_t>& ransac_stream(sfm_ctx* c, int n, int iters);
 
 // api_match.hip: the extraction's side of the operand owner record (MatchOperandsWs).
 // begin: with fused prep on, an extraction is about to write the operands of slots [0, B) of

@@ -201,6 +201,7 @@ void launch_u8_to_f32(const uint8_t* src, float* dst, int64_t n, hipStream_t st)
 // ransac.hip: CameraPose.find_inliers (SFM.py:126-160) for P correspondence sets
 // pts [P][nmax][4] int32 (x1, y1, x2, y2), sample indices idx (+ idx_off[p]) [iters][8].
 void ransac_sample_indices(int n, int iters, uint32_t seed, int32_t* out);
+void ransac_sample_indices_k(int n, int iters, uint32_t seed, int size, int32_t* out);  // [iters][size]
 void launch_ransac(const int32_t* pts, const int32_t* npts, int nmax, int P, const int32_t* idx,
                    const int32_t* idx_off, int iters, double thr, double* Fs, int32_t* counts, int32_t* out_pts,
                    int32_t* out_n, int32_t* out_iter, hipStream_t st);
@@ -250,6 +251,20 @@ constexpr int kLinkThreads = 256;
 int link_blocks(int nq);
 void launch_link_points(const int32_t* tgt, int m, const int32_t* qry, int nq, double threshold, int32_t* best,
                         int32_t* block_kept, int32_t* out_tgt, int32_t* out_qry, int32_t* out_n, hipStream_t st);
+
+// pnp.hip: the pose of a frame from its 2D-3D links.  X [n][3], x [n][2], K [9]
+// (upper triangular), idx [iters][stride] sample indices (the first 6 of a row are used).
+// launch_pnp_ransac: hypotheses, counts, selection and refinement; hyp [iters][12], counts
+// [iters], Rt [12] are workspace (counts may be the caller's table), out_status [4] = found,
+// LM status (kRefine*), accepted steps, iterations run; out_cost [2] = cost at the winning
+// hypothesis and at the returned pose.  launch_pnp: the DLT over all points, then the same
+// refinement.
+void launch_pnp_ransac(const double* X, const double* x, const double* K, int n, const int32_t* idx, int stride,
+                       int iters, double thr, int max_refine_iter, double* hyp, int32_t* counts, double* Rt,
+                       int32_t* out_inliers, int32_t* out_n, int32_t* out_iter, double* out_R, double* out_t,
+                       int32_t* out_status, double* out_cost, hipStream_t st);
+void launch_pnp(const double* X, const double* x, const double* K, int n, int max_refine_iter, double* Rt,
+                double* out_R, double* out_t, int32_t* out_status, double* out_cost, hipStream_t st);
 
 // registry.hip: the global 3-D point registry (SFMRunner.add_points, Runner.py:361-385;
 // DESIGN.md §13C).  reg_xyz [capacity][3] and *reg_count are the caller's device memory,

@@ -113,6 +113,12 @@ struct Cursor {
 }  // namespace
 
 void ransac_sample_indices(int n, int iters, uint32_t seed, int32_t* out) {
+  ransac_sample_indices_k(n, iters, seed, 8, out);
+}
+
+// the same stream with `size` (<= n) indices kept per iteration: np.random.choice(n, size,
+// replace=False) is permutation(n)[:size], a full shuffle whatever the size
+void ransac_sample_indices_k(int n, int iters, uint32_t seed, int size, int32_t* out) {
   Cursor g(raw_stream(seed));
   std::vector<int32_t> a(std::max(n, 1));
   uint32_t top = 0;  // random_interval's mask for i = n - 1: the smallest 2^b - 1 >= i
@@ -136,7 +142,7 @@ void ransac_sample_indices(int n, int iters, uint32_t seed, int32_t* out) {
       a[i] = a[v];
       a[v] = t;
     }
-    for (int k = 0; k < 8; ++k) out[(size_t)it * 8 + k] = a[k];
+    for (int k = 0; k < size; ++k) out[(size_t)it * size + k] = a[k];
   }
 }
 

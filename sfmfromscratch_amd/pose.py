@@ -18,6 +18,8 @@ At the end: what SFMRunner.perform does with the triangulated points — refinem
 of the next pair (refine.hip) — and then with every batch of them: the
 global point registry (SFMRunner.add_points), prepare_for_ba and total_reprojection_error
 (PointRegistry; registry.hip), with a host stand-in for cv2.Rodrigues.
+Between the two: the pose of every frame after the second from its 2D-3D links (PnPRansac, PnP,
+next_structure; pnp.hip) — the library's own rule, OpenCV parity not pinned.
 """
 from __future__ import annotations
 
@@ -501,6 +503,175 @@ def initial_structure(p1, p2, K1, K2, max_iterations, threshold=1.0, device: int
     X = non_linear_triangulation(_triangulate(a, b, A, B, False, device), a, b, A, B)
     mean, _ = _reprojection_dev(X, a, b, A, B, dev)
     return R2, t2, in1, in2, X.cpu().numpy(), float(mean.cpu()[0])
+
+
+# ---------------- the pose of the next frame: PnP (pnp.hip, DESIGN.md §13D) ----------------
+
+PNP_THRESHOLD = 8.0            # cv2.solvePnPRansac's reprojectionError of PoseEstimator.py:59
+PNP_MIN_POINTS = 6             # the minimal solver is a 6-point DLT
+
+
+def sample_indices_k(n: int, iters: int, size: int, seed: int = 5) -> np.ndarray:
+    """[iters, size] int32: np.random.seed(seed); [np.random.choice(n, size, replace=False) ...]
+    (`sample_indices` with the sample size as an argument; host only)."""
+    import ctypes
+    out = np.empty((max(iters, 0), size), np.int32)
+    check(load_library().sfm_ransac_sample_indices_k(int(n), int(iters), ctypes.c_uint32(seed), int(size),
+                                                     out.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+    return out
+
+
+def _pnp_inputs(points3d, points2d, K, dist_coeffs, device, what):
+    """-> (X [n, 3], x [n, 2], K [9]) float64 device tensors, host flag, device; None for X when
+    there are no points at all."""
+    import torch
+    if dist_coeffs is not None:
+        raise NotImplementedError(f"{what}: lens distortion is not supported (dist_coeffs must be None)")
+    if K is None:
+        raise ValueError(f"{what}: K is required")
+    host = not _is_dev(points3d)
+    dev = torch.device("cuda", device) if host else points3d.device
+    s3, s2 = _shape_of(points3d), _shape_of(points2d)
+    n = s3[0] if len(s3) else 0
+    if int(np.prod(s3)) == 0 or int(np.prod(s2)) == 0:  # np.array([]) of a frame without links
+        return None, None, None, host, dev
+    if len(s3) != 2 or s3[1] != 3 or s2 != (n, 2):
+        raise ValueError(f"{what}: points3d must be [n, 3] and points2d [n, 2]")
+    Kh = (K.cpu().numpy() if isinstance(K, torch.Tensor) else np.asarray(K)).astype(np.float64).reshape(-1)
+    if Kh.size != 9:
+        raise ValueError(f"{what}: K is 3 x 3")
+    if not np.isfinite(Kh).all():
+        raise ValueError(f"{what}: points3d, points2d and K must be finite")
+    if Kh[3] != 0 or Kh[6] != 0 or Kh[7] != 0 or Kh[0] == 0 or Kh[4] == 0 or Kh[8] == 0:
+        raise ValueError(f"{what}: K must be upper triangular with a non-zero diagonal")
+    fin = (lambda a: bool(torch.isfinite(a).all())) if not host else (lambda a: bool(np.isfinite(np.asarray(a)).all()))
+    if not (fin(points3d) and fin(points2d)):
+        raise ValueError(f"{what}: points3d, points2d and K must be finite")
+    if n < PNP_MIN_POINTS:  # no pose, and no device call
+        return None, None, None, host, dev
+    return _f64_dev(points3d, (n, 3), dev), _f64_dev(points2d, (n, 2), dev), _f64_dev(Kh, (9,), dev), host, dev
+
+
+def _pnp_ransac_dev(X, x, K, iters, threshold, max_refine_iter, dev, ctx=None):
+    """One sfm_pnp_ransac_dev call over device tensors (on the thread's context unless one is
+    given) -> dict of device tensors."""
+    import torch
+    n = int(X.shape[0])
+    i32 = lambda k: torch.empty(max(k, 1), dtype=torch.int32, device=dev)
+    f64 = lambda k: torch.empty(k, dtype=torch.float64, device=dev)
+    o = dict(R=f64(9), t=f64(3), inliers=i32(n), n=i32(1), iteration=i32(1), status=i32(4), cost=f64(2),
+             counts=i32(iters))
+    own, stream = _structure_ctx(dev)
+    ctx = ctx or own
+    check(ctx.lib.sfm_pnp_ransac_dev(ctx.handle, X.data_ptr(), x.data_ptr(), K.data_ptr(), n, int(iters),
+                                     float(threshold), int(max_refine_iter), o["R"].data_ptr(), o["t"].data_ptr(),
+                                     o["inliers"].data_ptr(), o["n"].data_ptr(), o["iteration"].data_ptr(),
+                                     o["status"].data_ptr(), o["cost"].data_ptr(), o["counts"].data_ptr(),
+                                     stream or None), ctx.handle)
+    return o
+
+
+def _pnp_info(info, status, cost, iteration=None, counts=None):
+    if info is None:
+        return
+    st = status.cpu().numpy()
+    c = cost.cpu().numpy()
+    info.update(status=int(st[1]), iters=int(st[2]), lm_iters=int(st[3]), cost0=float(c[0]), cost=float(c[1]))
+    if iteration is not None:
+        info.update(iteration=int(iteration.cpu()[0]), counts=counts.cpu().numpy())
+
+
+class PnPRansac:
+    """Stands in for PoseEstimator.PnPRansac (PoseEstimator.py:32-69; Runner.py:257-262) with the
+    library's own rule (include/sfmfeat.h sfm_pnp_ransac_dev): 6-point DLT
+    hypotheses from the np.random.seed(5) sample stream, inliers under 8 pixels of reprojection
+    error, the first sample with the most inliers, Levenberg-Marquardt refinement on its inliers.
+    Parity with cv2.solvePnPRansac is not pinned.
+
+    Attributes as the reference's: R [3, 3] float64 or None, t [3, 1] (cv2's tvec shape),
+    inliers int32 [k, 1] ascending (cv2's shape) or None.  Fewer than 6 points, or no sample with
+    an inlier, leaves all three None (Runner.py:263 then raises).  numpy or CPU tensors in, numpy
+    out; device tensors in, device tensors out.  Float32 input (Runner.py:258-259) converts
+    exactly.  dist_coeffs other than None raises NotImplementedError; non-finite input raises
+    ValueError.  info (optional dict) receives "iteration" (the winning sample, -1 for none),
+    "counts" [ransac_max_it], "cost0" / "cost" (sum of squared residuals over the inliers before
+    and after the refinement), "status" (REFINE_STATUS; -1 without a pose), "iters" (accepted
+    steps) and "lm_iters" (iterations run)."""
+
+    def __init__(self, points3d, points2d, K=None, ransac_max_it=100, dist_coeffs=None, threshold=PNP_THRESHOLD,
+                 device: int = 0, info=None, **kwargs):
+        self.R = self.t = self.inliers = None
+        iters = int(ransac_max_it)
+        if iters < 0:
+            raise ValueError("PnPRansac: ransac_max_it is negative")
+        X, x, Kd, host, dev = _pnp_inputs(points3d, points2d, K, dist_coeffs, device, "PnPRansac")
+        if info is not None:
+            info.update(iteration=-1, counts=np.zeros(iters, np.int32), cost0=float("nan"), cost=float("nan"),
+                        status=-1, iters=0, lm_iters=0)
+        if X is None or int(X.shape[0]) < PNP_MIN_POINTS:
+            return
+        o = _pnp_ransac_dev(X, x, Kd, iters, threshold, REFINE_MAX_ITER, dev)
+        _pnp_info(info, o["status"], o["cost"], o["iteration"], o["counts"][:iters])
+        k = int(o["n"].cpu()[0])
+        if k <= 0:
+            return
+        R, t, inl = o["R"].reshape(3, 3), o["t"].reshape(3, 1), o["inliers"][:k].reshape(k, 1)
+        self.R, self.t, self.inliers = (R.cpu().numpy(), t.cpu().numpy(), inl.cpu().numpy()) if host else (R, t, inl)
+
+
+class PnP:
+    """Stands in for PoseEstimator.PnP (PoseEstimator.py:71-105): the DLT over all n >= 6 points,
+    then the refinement of `PnPRansac` over all of them (sfm_pnp_dev).  R, t as PnPRansac's;
+    inliers stays None.  info receives "cost0", "cost", "status", "iters", "lm_iters"."""
+
+    def __init__(self, points3d, points2d, K=None, dist_coeffs=None, device: int = 0, info=None, **kwargs):
+        import torch
+        self.R = self.t = self.inliers = None
+        X, x, Kd, host, dev = _pnp_inputs(points3d, points2d, K, dist_coeffs, device, "PnP")
+        if info is not None:
+            info.update(cost0=float("nan"), cost=float("nan"), status=-1, iters=0, lm_iters=0)
+        if X is None or int(X.shape[0]) < PNP_MIN_POINTS:
+            return
+        R = torch.empty(9, dtype=torch.float64, device=dev)
+        t = torch.empty(3, dtype=torch.float64, device=dev)
+        status = torch.empty(4, dtype=torch.int32, device=dev)
+        cost = torch.empty(2, dtype=torch.float64, device=dev)
+        ctx, stream = _structure_ctx(dev)
+        check(ctx.lib.sfm_pnp_dev(ctx.handle, X.data_ptr(), x.data_ptr(), Kd.data_ptr(), int(X.shape[0]),
+                                  REFINE_MAX_ITER, R.data_ptr(), t.data_ptr(), status.data_ptr(), cost.data_ptr(),
+                                  stream or None), ctx.handle)
+        _pnp_info(info, status, cost)
+        if int(status.cpu()[0]) != 1:
+            return
+        R, t = R.reshape(3, 3), t.reshape(3, 1)
+        self.R, self.t = (R.cpu().numpy(), t.cpu().numpy()) if host else (R, t)
+
+
+def next_structure(points_2d_prev, p3d, P_prev, p1, p2, K, ransac_max_it=100, dist_threshold=5.0, device: int = 0,
+                   info=None):
+    """Runner.py:241-282 in one call, as `initial_structure` is for :198-211: `link_points` of the
+    previous pair's second-image pixels (points_2d_prev, with their 3-D points p3d) to this
+    pair's matches (p1 in the previous frame, p2 in the next), `PnPRansac` on the links cast to
+    float32 (Runner.py:258-259), P_next = `calculate_projection_matrix`, then `triangulate`,
+    `non_linear_triangulation` and `reprojection_error` of (p1, p2) under (P_prev, P_next); the
+    new points stay on the device between the last three.  Returns (R3, t3, inliers,
+    result_prev, result_next, P_next, p3d_new, mean_error); R3 is None (and P_next, p3d_new,
+    mean_error with it) when no pose is found, where Runner.py:263 raises.  info (optional dict)
+    receives PnPRansac's entries."""
+    import torch
+    result_prev, result_next = link_points(points_2d_prev, p3d, p1, p2, dist_threshold=dist_threshold, device=device)
+    pe = PnPRansac(np.asarray(result_prev, dtype=np.float32), np.asarray(result_next, dtype=np.float32), K=K,
+                   ransac_max_it=ransac_max_it, device=device, info=info)
+    if pe.R is None:
+        return None, None, None, result_prev, result_next, None, None, None
+    P_next = calculate_projection_matrix(pe.R, pe.t, K)
+    dev = torch.device("cuda", device)
+    n = len(p1)
+    a, b = _f64_dev(np.asarray(p1), (n, 2), dev), _f64_dev(np.asarray(p2), (n, 2), dev)
+    A, B = _f64_dev(P_prev, (12,), dev), _f64_dev(P_next, (12,), dev)
+    X = non_linear_triangulation(_triangulate(a, b, A, B, False, device), a, b, A, B)
+    mean, _ = _reprojection_dev(X, a, b, A, B, dev)
+    return pe.R, pe.t, pe.inliers, result_prev, result_next, P_next, X.cpu().numpy(), float(mean.cpu()[0])
 
 
 # ---------------- the point registry and the BA-input score (registry.hip, DESIGN.md §13C) ----------------
