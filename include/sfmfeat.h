@@ -49,6 +49,9 @@ extern "C" {
 #define SFM_MAX_KSIZE 31 /* largest NMS ksize accepted */
 #define SFM_MAX_FW 64    /* largest feature_width accepted */
 #define SFM_MAX_LEVELS 12
+#define SFM_BA_MAX_CAMERAS 256              /* sfm_bundle_adjust_dev: n_cam */
+#define SFM_BA_MAX_POINTS (1 << 24)          /* n_pts */
+#define SFM_BA_MAX_OBSERVATIONS (1 << 26)    /* M */
 
 /*
  * POD mirror of the reference's `extractor_params` dict keys.  Defaults are the
@@ -344,6 +347,58 @@ int32_t sfm_pnp_ransac_dev(sfm_ctx* ctx, const double* X, const double* x, const
 int32_t sfm_pnp_dev(sfm_ctx* ctx, const double* X, const double* x, const double* K, int32_t n,
                     int32_t max_refine_iter, double* R, double* t, int32_t* out_status, double* out_cost,
                     void* stream);
+
+/* Bundle adjustment over the registry (Runner.py:294-306, SFM.py:405-464): the library's own
+ * Levenberg-Marquardt rule with the Schur complement, in place of scipy's
+ * least_squares(method='trf', jac='2-point', ftol=1e-2).  Which iterate scipy's TRF path stops
+ * at is NOT pinned; the minimum is (a numpy restatement, scipy's tight-tolerance
+ * minimum and the reference's own recorded run).  Float64 without contraction.
+ * cam_idx, pt_idx [M] int32, obs [M][2], camera_params [n_cam][6] (Rodrigues vector, t),
+ * K [n_cam][9] row-major, X [n_pts][3], cam_fixed [n_cam] uint8 (optional; non-zero: the camera
+ * does not move); all on the device.  All M observations count (compute_residuals zips them
+ * all; the first-num_points bound belongs to total_reprojection_error alone).
+ *  Unknowns: per camera R_c = Rodrigues(camera_params[c][0:3]) (the closed form of
+ *   sfm_total_reprojection_error_dev) and t_c; per point X_j.
+ *  Residual: r_o = pi(K_c (R_c X_j + t_c)) - obs[o]; cost = the sum of their squares.
+ *  Update: R_c <- exp([d omega_c]x) R_c, t_c <- t_c + d t_c, X_j <- X_j + d X_j.
+ *  Jacobian rows, a in {0, 1}: Y = R_c X_j, q = K_c (Y + t_c), g_a = (K_c[a] - (q_a / q_2) K_c[2]) / q_2;
+ *   camera block [Y x g_a, g_a], point block g_a^T R_c.
+ *  Blocks: U_c = sum J_c^T J_c, V_j = sum J_p^T J_p, W_cj = sum J_c^T J_p (over the duplicate
+ *   observations of one (c, j) too), g_c, g_j.  Damping U*_c = U_c + lambda diag U_c,
+ *   V*_j = V_j + lambda diag V_j.  A camera flagged in cam_fixed, a camera without an
+ *   observation and a point without an observation do not move: their block is the identity,
+ *   their gradient and W are zero.
+ *  Step: S = U* - sum_j W_j V*_j^-1 W_j^T, b = -g_c + sum_j W_j V*_j^-1 g_j, S d_c = b by a dense
+ *   Cholesky, d X_j = -V*_j^-1 (g_j + W_j^T d_c).  A pivot of V*_j or of S that is not positive
+ *   and finite, or a candidate cost that is not finite, rejects the step.
+ *  lambda starts at 1e-3; a step is accepted iff the cost is strictly smaller, then
+ *   lambda <- max(lambda / 10, 1e-12), else lambda <- 10 lambda.
+ *  Status: 0 an accepted step with (cost - cost_new) / cost <= ftol, or with
+ *   |d| <= 1e-14 max(1, |params|) (params: every t_c and X_j); 1 lambda > 1e12; 3 max_iter
+ *   iterations ran; 2 the start cost is not finite (everything returned unchanged).
+ * Outputs (device): out_camera_params [n_cam][6], out_X [n_pts][3],
+ * out_cost [2] (optional) = start and final cost, out_status [4] (optional) = status, accepted
+ * steps, iterations run, iterations with a rejected factorisation.  The rotation goes back to
+ * its principal Rodrigues vector on the device (the closed form of the Python rodrigues): a
+ * vector that came in with theta > pi comes out as its equivalent with theta <= pi.  A camera
+ * that does not move, and every row when no step was accepted, returns its input bits.
+ * M == 0 returns the inputs, cost 0 and status 0.
+ * Every sum runs in a fixed order — ascending observation index within a point; U_c and g_c
+ * ascending per lane over the camera's list (lane = position mod 64), then a butterfly over the
+ * 64 lanes; the rows of S over the camera's points in list order within each of the equal
+ * segments its list is cut into (a number fixed by n_cam), then the segments in order; the
+ * cost over 256 strided partial sums and a fixed tree — so two runs give the same bits.
+ * Enqueued on `stream`: max_iter rounds of ordinary launches, each of which returns at once
+ * when the device-resident stop word is set; no synchronisation (growing the workspace frees
+ * buffers).  One call at a time per context.  Indices within their tables are the caller's
+ * contract (values are clamped).  SFM_EINVAL: n_cam outside [1, 256], n_pts outside [0, 2^24],
+ * M outside [0, 2^26], M > 0 with n_pts < 1, a null pointer (but cam_fixed, out_cost,
+ * out_status), ftol < 0 or NaN, max_iter outside [1, 2^24). */
+int32_t sfm_bundle_adjust_dev(sfm_ctx* ctx, const int32_t* cam_idx, const int32_t* pt_idx, const double* obs,
+                              int64_t M, const double* camera_params, int32_t n_cam, const double* K,
+                              const double* X, int32_t n_pts, const uint8_t* cam_fixed, double ftol,
+                              int32_t max_iter, double* out_camera_params, double* out_X, double* out_cost,
+                              int32_t* out_status, void* stream);
 
 /* sfm_ingest_rgb for B frames: rgb [B][H][W][3] uint8 -> gray [B][H2][W2] float32. */
 int32_t sfm_ingest_rgb_dev(sfm_ctx* ctx, const uint8_t* rgb, int32_t B, int32_t H, int32_t W,

@@ -25,6 +25,9 @@ SFM_MAX_GAUSS = 15
 SFM_MAX_KSIZE = 31
 SFM_MAX_FW = 64
 SFM_MAX_LEVELS = 12
+SFM_BA_MAX_CAMERAS = 256          # sfm_bundle_adjust_dev: n_cam
+SFM_BA_MAX_POINTS = 1 << 24       # n_pts
+SFM_BA_MAX_OBSERVATIONS = 1 << 26  # M
 
 
 class SfmParams(ctypes.Structure):

@@ -74,6 +74,9 @@ SIGNATURES = {
     "sfm_pnp_ransac_dev": (ctypes.c_int32, [_vp, _vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_double,
                                             ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sfm_pnp_dev": (ctypes.c_int32, [_vp, _vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    "sfm_bundle_adjust_dev": (ctypes.c_int32, [_vp, _vp, _vp, _vp, ctypes.c_int64, _vp, ctypes.c_int32, _vp, _vp,
+                                               ctypes.c_int32, _vp, ctypes.c_double, ctypes.c_int32, _vp, _vp, _vp,
+                                               _vp, _vp]),
     "sfm_ingest_rgb_dev": (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                             ctypes.c_int32, ctypes.c_int32, _vp, _vp]),
     "sfm_extract_batch_dev": (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp,

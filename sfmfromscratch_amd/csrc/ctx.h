@@ -9,6 +9,7 @@
 //                    c->registry  (the point registry's partials and per-point state)
 //   api_pnp.hip      c->pnp (sample stream on the device, hypotheses, counts; the host streams
 //                    are c->ransac's cache)
+//   api_ba.hip       c->ba (the plan's lists, the linearisation, the Schur system, the LM state)
 //   api_profile.hip  c->prof   (stage events, Harris spans, the sfm_debug_* reads)
 #pragma once
 
@@ -181,6 +182,12 @@ struct PnpWs {
   int idx_n = -1, idx_iters = -1, idx_stride = 0;
 };
 
+// Bundle adjustment (sfm_bundle_adjust_dev): everything kernels.h BaProblem points at between
+// its inputs and its outputs.  One call at a time per context.
+struct BaWs {
+  DevBuf st, Rt, Xs, cam_i, pt_cnt, pt_off, pt_list, pos, lin, e2, pts, lcam, Wm, Y, S, Spart, vec, nrm;
+};
+
 struct sfm_ctx {
   CtxStreams s;  // (first: outlives the workspaces below)
   int device = 0;
@@ -202,6 +209,7 @@ struct sfm_ctx {
   StructWs structure;
   RegistryWs registry;
   PnpWs pnp;
+  BaWs ba;
   // the workspaces free their buffers after this body, the streams and events go last
   ~sfm_ctx() {
     (void)hipSetDevice(device);

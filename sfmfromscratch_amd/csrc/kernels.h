@@ -286,6 +286,60 @@ void launch_total_reproj(const int32_t* cam_idx, const int32_t* pt_idx, const do
                          const double* cams, int n_cam, const double* K, const double* X, int n_pts, double* err,
                          double* mean, hipStream_t st);
 
+// ba.hip: bundle adjustment (Runner.py:294-306), the library's own Schur-complement
+// Levenberg-Marquardt (include/sfmfeat.h sfm_bundle_adjust_dev).  BaState is the
+// device-resident LM state; BaProblem the call's inputs, workspace (api_ba.hip sizes it) and
+// outputs, passed to every kernel by value.  Status values are kRefine*.
+// (include/sfmfeat.h SFM_BA_MAX_*; api_ba.hip asserts they agree)
+constexpr int kBaMaxCams = 256;       // the S row of one camera fits in LDS (72 KiB)
+constexpr int kBaMaxPoints = 1 << 24;
+constexpr int kBaMaxObs = 1 << 26;
+constexpr int kBaMaxSplit = 64;                      // segments a camera's list is cut into for the Schur rows
+constexpr size_t kBaSchurBudget = (size_t)64 << 20;  // bytes of partial rows (3 segments at 256 cameras)
+struct BaState {
+  double lam, cost, cost0;
+  int32_t cur;       // the slot of Rt / Xs that holds the accepted state
+  int32_t done;      // set by k_ba_decide: every later launch of the call returns at once
+  int32_t status, accepted, iters, rejected;
+  int32_t fail;      // a pivot of V*_j or of S was not positive and finite this iteration
+};
+struct BaProblem {
+  const int32_t* cam_idx;  // [M]
+  const int32_t* pt_idx;   // [M]
+  const double* obs;       // [M][2]
+  int M;
+  const double* cams_in;   // [n_cam][6]
+  int n_cam;
+  const double* K;         // [n_cam][9]
+  const double* X_in;      // [n_pts][3]
+  int n_pts;
+  const uint8_t* cam_fixed;  // [n_cam] or null
+  double ftol;
+  int max_iter;
+  BaState* st;
+  double* Rt;              // [2][n_cam][12]: R row-major, t
+  double* Xs;              // [2][n_pts][3]
+  int32_t *cam_cnt, *cam_off, *cam_list, *cam_active;  // [n_cam], [n_cam + 1], [M], [n_cam]
+  int32_t *pt_cnt, *pt_off, *pt_list, *pos;            // [n_pts], [n_pts + 1], [M], [M]
+  double* lin;             // [M][20]: r, J_c rows, J_p rows
+  double* e2;              // [M] squared residuals of the state being scored
+  double *vinv, *gp, *vg;  // [n_pts][6], [n_pts][3], [n_pts][3]
+  int32_t* lcam;           // [M] by list position: the camera of a merged W block, or -1
+  double *Wm, *Y;          // [M][18] by list position: W_cj and W_cj V*_j^-1 (6 x 3 row-major)
+  double *S, *b, *delta;   // [6 n_cam][6 n_cam], [6 n_cam], [6 n_cam]
+  double* Spart;           // [n_cam][schur_split][36 n_cam + 6]: each list segment's share of S's rows and of b
+  int schur_split;         // ba_schur_split(n_cam)
+  double* nrm;             // [n_pts + n_cam][2]
+  double* out_cams;        // [n_cam][6]
+  double* out_X;           // [n_pts][3]
+  double* out_cost;        // [2] or null
+  int32_t* out_status;     // [4] or null
+};
+// M >= 1, 1 <= n_cam <= kBaMaxCams, n_pts >= 1; cam_cnt and pt_cnt zeroed on the stream before
+int ba_schur_split(int n_cam);
+size_t ba_schur_lds_bytes(int n_cam);
+void launch_bundle_adjust(const BaProblem& p, hipStream_t st);
+
 // ingest.hip: PIL BICUBIC resize of [B][H][W][3] u8 RGB to H2 x W2 + /255 + _rgb2gray
 // (Runner.py:33-46) -> [B][H2][W2] float32; tmp holds [B][H][W2][3] u8.  Tables from
 // build_resample_table (host, Pillow's double-precision taps in 22-bit fixed point).

@@ -20,6 +20,9 @@ global point registry (SFMRunner.add_points), prepare_for_ba and total_reproject
 (PointRegistry; registry.hip), with a host stand-in for cv2.Rodrigues.
 Between the two: the pose of every frame after the second from its 2D-3D links (PnPRansac, PnP,
 next_structure; pnp.hip) — the library's own rule, OpenCV parity not pinned.
+Last: bundle adjustment over the registry (BundleAdjustment; ba.hip) — the
+library's own Schur-complement Levenberg-Marquardt; scipy's stopping iterate is not pinned, the
+minimum is.
 """
 from __future__ import annotations
 
@@ -880,6 +883,17 @@ class PointRegistry:
                 info["errors"] = err[:M].cpu().numpy()
             return float(mean.cpu()[0])
 
+    def set_points_3d(self, X):
+        """Runner.py:304 (global_points_3D = the adjusted points): writes X [len(self), 3] (numpy
+        or a device tensor) over the registered coordinates; the count, the indices and the
+        observations stay.  `save` then writes the adjusted model.  ValueError on any other
+        shape.  (Later add_points calls compare against the adjusted coordinates.)"""
+        n = len(self)
+        if _shape_of(X) != (n, 3):
+            raise ValueError(f"set_points_3d: X must be [{n}, 3], the registered count")
+        if n:
+            self._table[:n].copy_(_f64_dev(X, (n, 3), self._dev))
+
     def save(self, path):
         """SFMRunner.save_data's file (Runner.py:357-359): p3d, frame_idx, pt_idx."""
         np.savez(path, p3d=self.points_3d, frame_idx=self.frame_indices, pt_idx=self.point_indices)
@@ -904,3 +918,104 @@ class PointRegistry:
             r._idx.append(torch.from_numpy(pt.astype(np.int32)).to(r._dev))
             r._frames.append(torch.from_numpy(fr).to(r._dev))
         return r
+
+
+# ---------------- bundle adjustment (ba.hip) ----------------
+
+BA_MAX_CAMERAS = _abi.SFM_BA_MAX_CAMERAS
+BA_MAX_POINTS = _abi.SFM_BA_MAX_POINTS
+BA_MAX_OBSERVATIONS = _abi.SFM_BA_MAX_OBSERVATIONS
+
+
+class BundleAdjustment:
+    """Stands in for SFM.BundleAdjustment (SFM.py:405-464; Runner.py:294-303) with the library's
+    own rule (include/sfmfeat.h sfm_bundle_adjust_dev): Levenberg-Marquardt with
+    the Schur complement over every camera's (R, t) and every point, Marquardt damping, strict
+    acceptance, stopping at the first accepted step whose relative decrease is <= ftol (the
+    reference's 1e-2 by default).  Which iterate scipy's TRF path stops at is not pinned; the
+    minimum is.  All observations count, as compute_residuals zips them all.
+
+    The constructor takes the reference's arguments (the tuple of PointRegistry.prepare_for_ba);
+    arrays are numpy or device tensors.  fixed_cameras (optional): a boolean mask [num_cameras] or
+    a list of camera indices that do not move.  numpy indices outside their tables raise
+    IndexError (device indices are the caller's contract).  info (optional dict) receives
+    "cost0", "cost" (the sum of squared residuals before and after), "status" (REFINE_STATUS),
+    "iters" (accepted steps), "lm_iters" (iterations run) and "rejected_factorisations"."""
+
+    def __init__(self, num_cameras, num_points, camera_indices, point_indices, points_2d, camera_params, points_3d,
+                 K_list, device: int = 0, fixed_cameras=None, ftol=1e-2, max_iter=50, info=None):
+        self.num_cameras, self.num_points = int(num_cameras), int(num_points)
+        self.camera_indices, self.point_indices, self.points_2d = camera_indices, point_indices, points_2d
+        self.camera_params, self.points_3d, self.K_list = camera_params, points_3d, K_list
+        self.device, self.fixed_cameras, self.ftol, self.max_iter, self.info = device, fixed_cameras, ftol, max_iter, info
+
+    def sparse_bundle_adjustment(self, as_device: bool = False):
+        """-> (optimized_camera_params [num_cameras, 6], optimized_points_3d [num_points, 3]):
+        float64 numpy, or device tensors with as_device=True (nothing synchronises then unless
+        info is given)."""
+        import torch
+        n_cam, n_pts = self.num_cameras, self.num_points
+        ftol, max_iter = float(self.ftol), int(self.max_iter)
+        if not 1 <= n_cam <= BA_MAX_CAMERAS:
+            raise ValueError(f"BundleAdjustment: num_cameras must be in [1, {BA_MAX_CAMERAS}]")
+        if not 0 <= n_pts <= BA_MAX_POINTS:
+            raise ValueError("BundleAdjustment: num_points must be in [0, 2^24]")
+        if not ftol >= 0:
+            raise ValueError("BundleAdjustment: ftol must be >= 0")
+        if not 1 <= max_iter < (1 << REFINE_STATUS_SHIFT):
+            raise ValueError("BundleAdjustment: max_iter must be in [1, 2^24)")
+        probe = next((a for a in (self.points_3d, self.camera_params, self.points_2d) if _is_dev(a)), None)
+        dev = probe.device if probe is not None else torch.device("cuda", self.device)
+        with torch.cuda.device(dev):
+            cams = _f64_dev(self.camera_params, (-1, 6), dev)
+            K = _f64_dev(self.K_list, (-1, 3, 3), dev)
+            X = _f64_dev(self.points_3d, (-1, 3), dev)
+            obs = _f64_dev(self.points_2d, (-1, 2), dev)
+            M = int(obs.shape[0])
+            if M > BA_MAX_OBSERVATIONS:
+                raise ValueError("BundleAdjustment: at most 2^26 observations")
+            if int(cams.shape[0]) != n_cam or int(X.shape[0]) != n_pts:
+                raise ValueError("BundleAdjustment: camera_params must be [num_cameras, 6] and points_3d [num_points, 3]")
+            if int(K.shape[0]) < n_cam:
+                raise ValueError("BundleAdjustment: K_list has fewer entries than camera_params")
+            for a, hi, what in ((self.camera_indices, n_cam, "camera"), (self.point_indices, n_pts, "point")):
+                if int(np.prod(_shape_of(a))) != M:
+                    raise ValueError(f"BundleAdjustment: {what}_indices must have one entry per observation")
+                if not _is_dev(a) and M:
+                    h = np.asarray(a).reshape(-1)
+                    if h.min() < 0 or h.max() >= hi:
+                        raise IndexError(f"BundleAdjustment: a {what} index is outside its table")
+            ci = _i32_dev(self.camera_indices, M, dev, "camera_indices")
+            pi = _i32_dev(self.point_indices, M, dev, "point_indices")
+            fixed = None
+            if self.fixed_cameras is not None:
+                f = self.fixed_cameras.cpu().numpy() if isinstance(self.fixed_cameras, torch.Tensor) \
+                    else np.asarray(self.fixed_cameras)
+                mask = np.zeros(n_cam, np.uint8)
+                if f.dtype == np.bool_:
+                    if f.shape != (n_cam,):
+                        raise ValueError("BundleAdjustment: a fixed_cameras mask must be [num_cameras]")
+                    mask[f] = 1
+                elif f.size:
+                    f = f.astype(np.int64).reshape(-1)
+                    if f.min() < 0 or f.max() >= n_cam:
+                        raise IndexError("BundleAdjustment: a fixed camera index is outside its table")
+                    mask[f] = 1
+                fixed = torch.from_numpy(mask).to(dev)
+            out_c = torch.empty((n_cam, 6), dtype=torch.float64, device=dev)
+            out_X = torch.empty((n_pts, 3), dtype=torch.float64, device=dev)
+            cost = torch.empty(2, dtype=torch.float64, device=dev)
+            status = torch.empty(4, dtype=torch.int32, device=dev)
+            ctx, stream = _structure_ctx(dev)
+            check(ctx.lib.sfm_bundle_adjust_dev(
+                ctx.handle, ci.data_ptr(), pi.data_ptr(), obs.data_ptr(), M, cams.data_ptr(), n_cam, K.data_ptr(),
+                X.data_ptr() if n_pts else None, n_pts, fixed.data_ptr() if fixed is not None else None, ftol,
+                max_iter, out_c.data_ptr(), out_X.data_ptr() if n_pts else None, cost.data_ptr(), status.data_ptr(),
+                stream or None), ctx.handle)
+            if self.info is not None:
+                st, c = status.cpu().numpy(), cost.cpu().numpy()
+                self.info.update(cost0=float(c[0]), cost=float(c[1]), status=int(st[0]), iters=int(st[1]),
+                                 lm_iters=int(st[2]), rejected_factorisations=int(st[3]))
+            if as_device:
+                return out_c, out_X
+            return out_c.cpu().numpy(), out_X.cpu().numpy()
