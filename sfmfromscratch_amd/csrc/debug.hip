@@ -139,7 +139,9 @@ int32_t sfm_debug_nms(int32_t device, const float* R, int32_t B, int32_t H, int3
 }
 
 // Mean time (ms) of one k_harris<7> launch over B x H x W synthetic planes for ablation
-// variant `abl` (0 full, 1 no histogram, 2 no window sums, 3 no Sobel/products).
+// variant `abl` (harris.hip ABL: 0 full, 1 no histogram, 2 window over the first tap row, 4 no
+// barriers; diagnostic build only: 5 no scalar tap loads in the window — the full kernel runs
+// in its place in the shipped library).
 float sfm_debug_time_harris(int32_t device, int32_t abl, int32_t B, int32_t H, int32_t W, int32_t iters) {
   return sfm_debug_harris_stamps(device, abl, B, H, W, iters, nullptr, 0);
 }

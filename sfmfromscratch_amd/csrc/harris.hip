@@ -103,7 +103,9 @@ __device__ __forceinline__ void pk_fma_bcast(f32x2& acc, f32x2 k, f32x2 v) {
 //
 // ABL (timing builds only): 0 = full kernel, 1 = no digit histogram, 2 = window sums over
 // the first tap row only, 3 = full kernel + per-workgroup timestamps into g_harris_stamps,
-// 4 = no workgroup barriers in the tile loop (LDS races: results wrong; the barriers' cost).
+// 4 = no workgroup barriers in the tile loop (LDS races: results wrong; the barriers' cost),
+// 5 = every window block uses tap row 0's pairs, loaded once per tile (results wrong; the
+// cost of the window's scalar tap loads).
 // ABL = 3 diagnostics: per workgroup kStampSlots u64 = {start, end, cu id, tiles, end of
 // each tile ...} (s_memrealtime, 100 MHz)
 constexpr int kStampSlots = 48;
@@ -172,6 +174,46 @@ struct MfWin {
   }
 };
 
+// The VALU window's schedule: a thread's window sums are a sequence of blocks, one per
+// (gradient row r, output row pair p) whose tap rows r - 2p (first output row of the pair) or
+// r - 2p - 1 (second) exist — 4 columns x 3 products x KS taps instructions each (84 at KS 7).
+// Block k needs one set of KS tap pairs (tap row d = r - 2p, harris_taps_build) and the row's
+// products.  Its taps are loaded while block k - 1 runs, into the set block k - 2 used, and a
+// row's gradients are read from LDS while the last block of the row before runs, so every load
+// has a block of fmas between its issue and the wait that retires it.
+template <int KS, int NPAIR, int ABL>
+struct WinBlocks {
+  static constexpr int NR = (ABL == 2) ? 1 : KS + 2 * NPAIR - 1;  // gradient rows feeding a thread
+  static constexpr bool v0(int r, int p) { return r - 2 * p >= 0 && r - 2 * p < KS && (ABL != 2 || r - 2 * p == 0); }
+  static constexpr bool v1(int r, int p) { return r - 2 * p - 1 >= 0 && r - 2 * p - 1 < KS && ABL != 2; }
+  static constexpr int count(int r_end) {  // blocks of gradient rows < r_end
+    int n = 0;
+    for (int r = 0; r < r_end; ++r)
+      for (int p = 0; p < NPAIR; ++p) n += (v0(r, p) || v1(r, p)) ? 1 : 0;
+    return n;
+  }
+  static constexpr int NB = count(NR);
+  static constexpr int row(int k) {
+    int r = 0;
+    while (count(r + 1) <= k) ++r;
+    return r;
+  }
+  static constexpr int pair(int k) {
+    const int r = row(k);
+    int n = count(r);
+    for (int p = 0; p < NPAIR; ++p)
+      if (v0(r, p) || v1(r, p)) {
+        if (n == k) return p;
+        ++n;
+      }
+    return 0;
+  }
+  static constexpr bool first_of_row(int k) { return k == count(row(k)); }
+  static constexpr bool last_of_row(int k) { return k + 1 == count(row(k) + 1); }
+};
+// s_waitcnt lgkmcnt(0) alone (gfx9 encoding: vmcnt 63, expcnt 7 = no wait)
+constexpr int kWaitLgkm0 = 0xC07F;
+
 template <int KS, bool VEC, int ABL = 0, int F = 0>
 __global__ void __launch_bounds__(HarrisShape<F>::NT, HarrisShape<F>::WPE) k_harris(HarrisLevels lvs, const float* __restrict__ gk, float alpha) {
   constexpr int NT = HarrisShape<F>::NT, RPT = HarrisShape<F>::RPT, NPAIR = HarrisShape<F>::NPAIR;
@@ -187,9 +229,7 @@ __global__ void __launch_bounds__(HarrisShape<F>::NT, HarrisShape<F>::WPE) k_har
   for (int k = 1; k < kHarrisMaxLevels; ++k) li += (k < lvs.n && (int)blockIdx.x >= lvs.l[k].wg0) ? 1 : 0;
   const float* __restrict__ lvl = lvs.l[li].lvl;
   float* __restrict__ Rout = lvs.l[li].R;
-  uint32_t* __restrict__ hist_g = lvs.l[li].hist;
   const int H = lvs.l[li].H, W = lvs.l[li].W, tiles_x = lvs.l[li].tiles_x, ntiles = lvs.l[li].ntiles;
-  const SelectScan scan = lvs.l[li].scan;
   const int wgx = (int)blockIdx.x - lvs.l[li].wg0, nwg = lvs.l[li].nwg;  // workgroups of this level's plane
   constexpr int GA = KS / 2;
   constexpr int PH = TH + KS - 1;           // gradient rows of a tile (window halo)
@@ -340,10 +380,26 @@ __global__ void __launch_bounds__(HarrisShape<F>::NT, HarrisShape<F>::WPE) k_har
     const int tx0 = (tile % tiles_x) * kHT;
     const int ty0 = (tile / tiles_x) * TH;
     // tap pairs (harris_taps_build): pair (d, j) = (g[d][j], g[d-1][j]) for d = 0..KS, a
-    // missing tap row 0.  The pointer is laundered once per tile so the compiler re-issues the
-    // scalar loads per gradient row instead of hoisting all (KS+1) x KS pairs into SGPRs
+    // missing tap row 0.  Two sets of KS pairs, alternating per window block (WinBlocks).  The
+    // pointer is laundered at every set's load so the compiler issues the scalar loads there
+    // instead of hoisting all (KS+1) x KS pairs into SGPRs
+    using WB = WinBlocks<KS, NPAIR, ABL>;
     const cf32x2* tp = (const cf32x2*)(gk + kHarrisPairOff);
-    asm volatile("" : "+s"(tp));
+    f32x2 T[2][KS];
+    auto load_taps = [&](auto kc) {  // block k's set
+      constexpr int k = decltype(kc)::value;
+      if constexpr (ABL == 5) {
+        if constexpr (k == 0) {
+#pragma unroll
+          for (int j = 0; j < KS; ++j) T[0][j] = tp[j];
+        }
+      } else {
+        constexpr int d = WB::row(k) - 2 * WB::pair(k);  // tap rows (d, d - 1) of the pair's two output rows
+        asm volatile("" : "+s"(tp));
+#pragma unroll
+        for (int j = 0; j < KS; ++j) T[k & 1][j] = tp[d * KS + j];
+      }
+    };
     if constexpr (ABL != 4) __syncthreads();  // the previous tile's LDS reads are done
     // 0. the prefetched image tile -> LDS, then start fetching the next tile (a tile whose
     //    whole image window lies inside the image stores its loads unmasked)
@@ -472,6 +528,11 @@ __global__ void __launch_bounds__(HarrisShape<F>::NT, HarrisShape<F>::WPE) k_har
     const bool grad_in = SFM_INTERIOR(tx0 - GA >= 0 && tx0 - GA + PWP <= W && ty0 - GA >= 0 && ty0 - GA + PH <= H);
     if (grad_in) sobel(std::false_type{});
     else sobel(std::true_type{});
+    // the first window block's taps do not depend on LDS: their loads fly across the barrier
+    if constexpr (!MF) {
+      load_taps(std::integral_constant<int, 0>{});
+      __builtin_amdgcn_sched_barrier(0);
+    }
     if constexpr (ABL != 4) __syncthreads();
     if constexpr (F == 0) {
       // fused pyramid: the tile's 8 x 8 blocks of this level -> the next three exact 2x levels
@@ -616,10 +677,16 @@ __global__ void __launch_bounds__(HarrisShape<F>::NT, HarrisShape<F>::WPE) k_har
     f32x4 macc2[HY ? 4 : 1];
 #pragma unroll
     for (int o = 0; o < (HY ? 4 : 1); ++o) macc2[o] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    constexpr int NR = (ABL == 2) ? 1 : KS + 2 * NPAIR - 1;  // gradient rows feeding this thread
-    static_for<NR>([&](auto rc) {
-      constexpr int r = decltype(rc)::value;
-      f32x2 P[3][NP2];
+    // The loads are software-pipelined by one block (WinBlocks) and their places are pinned
+    // with sched_barrier: lgkmcnt counts scalar loads and LDS reads together and scalar loads
+    // return out of order, so any wait on a tap is lgkmcnt(0) and drains whatever was issued
+    // just before it.  Every block therefore starts with the one wait that retires the loads
+    // issued at the start of the block before (its taps, its row's gradients), then issues the
+    // next block's loads, then runs its fmas behind them.
+    f32x2 P[3][NP2];                               // the current row's products
+    f32x2 X[PP ? 1 : NVP / 2], Y[PP ? 1 : NVP / 2];  // the next row's gradients
+    f32x2 Pn[PP ? 3 : 1][PP ? NP2 : 1];            // PP: the next row's products
+    auto load_row = [&](int r) {  // gradient row r: LDS -> X, Y (PP: the products -> Pn)
       if constexpr (PP) {
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl) {
@@ -627,76 +694,80 @@ __global__ void __launch_bounds__(HarrisShape<F>::NT, HarrisShape<F>::WPE) k_har
 #pragma unroll
           for (int c4 = 0; c4 < NV4; ++c4) {
             const float4 a = rp[c4];
-            if (2 * c4 < NP2) P[pl][2 * c4] = f32x2{a.x, a.y};
-            if (2 * c4 + 1 < NP2) P[pl][2 * c4 + 1] = f32x2{a.z, a.w};
+            if (2 * c4 < NP2) Pn[PP ? pl : 0][PP ? 2 * c4 : 0] = f32x2{a.x, a.y};
+            if (2 * c4 + 1 < NP2) Pn[PP ? pl : 0][PP ? 2 * c4 + 1 : 0] = f32x2{a.z, a.w};
           }
         }
       } else {
         const float4* rx = reinterpret_cast<const float4*>(&s_g[0][RPT * rq + r][4 * tq]);
         const float4* ry = reinterpret_cast<const float4*>(&s_g[1][RPT * rq + r][4 * tq]);
-        f32x2 X[NVP / 2], Y[NVP / 2];
 #pragma unroll
         for (int c4 = 0; c4 < NV4; ++c4) {
           const float4 a = rx[c4], c = ry[c4];
-          X[2 * c4] = f32x2{a.x, a.y};
-          X[2 * c4 + 1] = f32x2{a.z, a.w};
-          Y[2 * c4] = f32x2{c.x, c.y};
-          Y[2 * c4 + 1] = f32x2{c.z, c.w};
-        }
-#pragma unroll
-        for (int m = 0; m < NP2; ++m) {
-          P[0][m] = X[m] * X[m];
-          P[1][m] = Y[m] * Y[m];
-          P[2][m] = X[m] * Y[m];
+          X[PP ? 0 : 2 * c4] = f32x2{a.x, a.y};
+          X[PP ? 0 : 2 * c4 + 1] = f32x2{a.z, a.w};
+          Y[PP ? 0 : 2 * c4] = f32x2{c.x, c.y};
+          Y[PP ? 0 : 2 * c4 + 1] = f32x2{c.z, c.w};
         }
       }
-      f32x2 T[NPAIR][KS];
-      asm volatile("" : "+s"(tp));  // this row's pairs are loaded here, not hoisted with every row's
+    };
+    auto form_products = [&]() {  // the loaded row becomes the current one
 #pragma unroll
-      for (int p = 0; p < NPAIR; ++p) {
-        const int d = r - 2 * p;  // tap rows (d, d - 1) of the pair's two output rows
-        if (d >= 0 && d <= KS) {
+      for (int m = 0; m < NP2; ++m) {
+        if constexpr (PP) {
 #pragma unroll
-          for (int j = 0; j < KS; ++j) T[p][j] = tp[d * KS + j];
+          for (int pl = 0; pl < 3; ++pl) P[pl][m] = Pn[PP ? pl : 0][PP ? m : 0];
+        } else {
+          P[0][m] = X[PP ? 0 : m] * X[PP ? 0 : m];
+          P[1][m] = Y[PP ? 0 : m] * Y[PP ? 0 : m];
+          P[2][m] = X[PP ? 0 : m] * Y[PP ? 0 : m];
         }
       }
+    };
+    load_row(0);
+    static_for<WB::NB>([&](auto kc) {
+      constexpr int k = decltype(kc)::value, r = WB::row(k), p = WB::pair(k);
+      constexpr bool v0 = WB::v0(r, p), v1 = WB::v1(r, p);
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_waitcnt(kWaitLgkm0);
+      __builtin_amdgcn_sched_barrier(0);
+      if constexpr (k + 1 < WB::NB) load_taps(std::integral_constant<int, k + 1>{});
+      if constexpr (WB::first_of_row(k)) form_products();
+      __builtin_amdgcn_sched_barrier(0);
+      if constexpr (WB::last_of_row(k) && r + 1 < WB::NR) load_row(r + 1);
+      __builtin_amdgcn_sched_barrier(0);
+      const f32x2 (&Tk)[KS] = T[ABL == 5 ? 0 : (k & 1)];
 #pragma unroll
-      for (int p = 0; p < NPAIR; ++p) {
-        const int i0 = r - 2 * p, i1 = r - 2 * p - 1;  // tap rows of the pair's two rows
-        const bool v0 = i0 >= 0 && i0 < KS && (ABL != 2 || i0 == 0);
-        const bool v1 = i1 >= 0 && i1 < KS && ABL != 2;
-        if (!v0 && !v1) continue;  // (a compile-time condition)
+      for (int pl = 0; pl < (HY ? 2 : 3); ++pl)
 #pragma unroll
-        for (int pl = 0; pl < (HY ? 2 : 3); ++pl)
+        for (int j = 0; j < KS; ++j)
 #pragma unroll
-          for (int j = 0; j < KS; ++j)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              const int m = q + j;
-              if (v0 && v1) {
-                if (m & 1) pk_fma_bcast<1>(acc[p][pl][q], T[p][j], P[pl][m >> 1]);
-                else pk_fma_bcast<0>(acc[p][pl][q], T[p][j], P[pl][m >> 1]);
-              } else if (v0) {
-                acc[p][pl][q].x = __builtin_fmaf(T[p][j].x, P[pl][m >> 1][m & 1], acc[p][pl][q].x);
-              } else {
-                acc[p][pl][q].y = __builtin_fmaf(T[p][j].y, P[pl][m >> 1][m & 1], acc[p][pl][q].y);
-              }
+          for (int q = 0; q < 4; ++q) {
+            const int m = q + j;
+            if (v0 && v1) {
+              if (m & 1) pk_fma_bcast<1>(acc[p][pl][q], Tk[j], P[pl][m >> 1]);
+              else pk_fma_bcast<0>(acc[p][pl][q], Tk[j], P[pl][m >> 1]);
+            } else if (v0) {
+              acc[p][pl][q].x = __builtin_fmaf(Tk[j].x, P[pl][m >> 1][m & 1], acc[p][pl][q].x);
+            } else {
+              acc[p][pl][q].y = __builtin_fmaf(Tk[j].y, P[pl][m >> 1][m & 1], acc[p][pl][q].y);
             }
-      }
-      if constexpr (HY) {
+          }
+      if constexpr (HY && WB::last_of_row(k)) {
         // S_xy: gradient row r is tap row r - o of output row o; step s takes column 4tq + s
         // (the thread's own IxIy product) with the banded taps (MfWin)
         static_for<RPT>([&](auto oc) {
           constexpr int o = decltype(oc)::value, dy = r - o;
           if constexpr (dy >= 0 && dy < KS && (ABL != 2 || dy == 0)) {
             static_for<MNS>([&](auto sc) {
-              constexpr int st = decltype(sc)::value, k = dy * MNS + st;
-              macc2[o] = __builtin_amdgcn_mfma_f32_4x4x1f32(tapV[k / 16], P[2][st >> 1][st & 1], macc2[o], 4, k % 16, 0);
+              constexpr int st = decltype(sc)::value, ks = dy * MNS + st;
+              macc2[o] = __builtin_amdgcn_mfma_f32_4x4x1f32(tapV[ks / 16], P[2][st >> 1][st & 1], macc2[o], 4, ks % 16, 0);
             });
           }
         });
       }
     });
+    __builtin_amdgcn_sched_barrier(0);
     // 3. R = det - alpha * trace^2 (:71-74), digit-1 histogram of R, R stored as 16-B
     //    row segments (a wave writes 8 rows x 128 contiguous bytes per store); a tile wholly
     //    inside the plane counts and stores without per-pixel bounds
@@ -759,6 +830,10 @@ __global__ void __launch_bounds__(HarrisShape<F>::NT, HarrisShape<F>::WPE) k_har
     }
   }
   __syncthreads();
+  // (read here, not with the level's other fields: neither is used in the tile loop, which has
+  // no SGPRs to hold them)
+  uint32_t* __restrict__ hist_g = lvs.l[li].hist;
+  const SelectScan scan = lvs.l[li].scan;
   uint32_t* hg = hist_g + (int64_t)b * kMedBins1;
   for (int i = tid; i < kMedBins1; i += NT) {
     uint32_t c = s_hist[i] + (NHC == 2 ? s_hist[kHistCopy + i] : 0u);
@@ -955,6 +1030,9 @@ float time_harris_ablation(int abl, const float* lvl, float* R, uint32_t* hist, 
       case 2: launch_ks<7, 2>(g, B, gk, alpha, 0); break;
       case 3: launch_ks<7, 3>(g, B, gk, alpha, 0); break;
       case 4: launch_ks<7, 4>(g, B, gk, alpha, 0); break;
+#ifdef SFM_ABLATIONS
+      case 5: launch_ks<7, 5>(g, B, gk, alpha, 0); break;
+#endif
       default: launch_ks<7, 0>(g, B, gk, alpha, 0); break;
     }
   };

@@ -20,7 +20,10 @@ tile takes the interior-tile path: unmasked prefetch, tile copy, Sobel and epilo
 static count of the tile loop is exactly the VALU count per tile-wave of an interior tile — the
 tiles that do not touch the image border (all but 92 of the 510 per 1080p plane).  Without it
 the loop holds both variants of each masked phase and the count is an upper bound.
-usage: tools/isa_phases.py [--interior] [lib.so] [kernel-substring]"""
+With --loads it lists the window's scalar tap loads instead: for each, the VALU instructions
+between it and the first s_waitcnt on lgkmcnt after it (the work that covers its latency), and
+the SGPR spill moves (v_readlane / v_writelane) in the tile loop.
+usage: tools/isa_phases.py [--interior | --loads] [lib.so] [kernel-substring]"""
 import collections
 import os
 import re
@@ -85,7 +88,7 @@ def interior_object(tmp, no_down=False):
     out = os.path.join(tmp, "harris_interior%s.o" % ("_nd" if no_down else ""))
     subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
                     "-fno-fast-math", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-slp-vectorize",
-                    "-DSFM_HARRIS_COUNT_INTERIOR"] + (["-DSFM_HARRIS_COUNT_NO_DOWN"] if no_down else []) +
+                    "-mllvm", "-greedy-reverse-local-assignment", "-DSFM_HARRIS_COUNT_INTERIOR"] + (["-DSFM_HARRIS_COUNT_NO_DOWN"] if no_down else []) +
                    ["-c", src, "-o", out], check=True, stderr=subprocess.DEVNULL)
     return out
 
@@ -144,7 +147,56 @@ def phase_counts(ins):
     return cnt, (a, b), bars, inner, trips, win, sc
 
 
+def window_bounds(ins):
+    """(first, last) instruction index of the tile loop's window part: from the last s_barrier
+    of the tile loop (Sobel -> window) to the loop's closing branch."""
+    _, (a, b), bars, _, _, _, _ = phase_counts(ins)
+    return bars[-1], b
+
+
+def scalar_load_cover(ins):
+    """The tap loads (scalar) of the window part of the tile loop: for each, (offset in the tile
+    loop, instruction, VALU instructions up to the first s_waitcnt on lgkmcnt after it).  A
+    scalar load returns out of order, so that wait is lgkmcnt(0) and the VALU count is all the
+    work the wave has to cover the load's latency."""
+    _, (a, _), _, _, _, _, _ = phase_counts(ins)
+    w0, w1 = window_bounds(ins)
+    loads = [k for k in range(w0, w1 + 1) if ins[k][0].startswith("s_load_dword")]
+    # the tap table's loads share one base register pair; the few others read kernel arguments
+    # (the fused pyramid's level pointers)
+    bases = collections.Counter(ins[k][1].split(",")[1].strip() for k in loads)
+    tap_base = bases.most_common(1)[0][0] if bases else None
+    out = []
+    for k in loads:
+        if ins[k][1].split(",")[1].strip() != tap_base:
+            continue
+        valu = 0
+        for j in range(k + 1, w1 + 1):
+            if ins[j][0] == "s_waitcnt" and "lgkmcnt" in ins[j][1]:
+                break
+            valu += 1 if ins[j][0].startswith("v_") else 0
+        out.append((k - a, "%s %s" % ins[k][:2], valu))
+    return out
+
+
+def lane_moves(ins):
+    """v_readlane_b32 / v_writelane_b32 (SGPR spill moves) inside the tile loop."""
+    _, (a, b), _, _, _, _, _ = phase_counts(ins)
+    return sum(1 for k in range(a, b + 1) if ins[k][0] in ("v_readlane_b32", "v_writelane_b32"))
+
+
 def main():
+    if "--loads" in sys.argv[1:]:
+        args = [a for a in sys.argv[1:] if a != "--loads"]
+        lib = args[0] if args else os.path.join(ROOT, "sfmfromscratch_amd", "lib", "libsfmfeat.so")
+        name, ins = kernel_body(disassemble(lib), args[1] if len(args) > 1 else "k_harrisILi7ELb1ELi0ELi0E")
+        cover = scalar_load_cover(ins)
+        print(f"{name}: {len(cover)} scalar loads in the window part of the tile loop, "
+              f"{lane_moves(ins)} lane moves in the tile loop")
+        print(f"{'offset':>6s} {'VALU to the next lgkmcnt wait':>30s}  instruction")
+        for off, text, valu in cover:
+            print(f"{off:6d} {valu:30d}  {text}")
+        return
     args = [a for a in sys.argv[1:] if a != "--interior"]
     interior = "--interior" in sys.argv[1:]
     pat = args[1] if len(args) > 1 else "k_harrisILi7ELb1ELi0ELi0E"
