@@ -400,6 +400,56 @@ int32_t sfm_bundle_adjust_dev(sfm_ctx* ctx, const int32_t* cam_idx, const int32_
                               int32_t max_iter, double* out_camera_params, double* out_X, double* out_cost,
                               int32_t* out_status, void* stream);
 
+/* Feature tracks: the connected components of the match graph of a slot table, the step between
+ * pairwise matches and reconstruction in COLMAP / OpenMVG / openMVS.  The reference has none; the
+ * rule is the library's own, pinned to a numpy restatement and scipy's connected_components
+ * (DESIGN.md §13F).  No geometric verification is built in: `keep` carries the caller's.
+ * Inputs (device), in the layouts of sfm_match_pairs_dev: count [nimg], pairs [P][2],
+ * matches [P][cap][2], nmatch [P]; keep [P][cap] uint8 (optional; NULL: every match counts).
+ *  Nodes: (slot s, row r) with r < count[s] (count clamped to [0, cap]); id = s * cap + r.
+ *  Edges: for each pair p and each m < nmatch[p] (nmatch = -1 counts as 0, values above cap as
+ *   cap) with keep[p][m] != 0, an edge between (pairs[p][0], matches[p][m][0]) and
+ *   (pairs[p][1], matches[p][m][1]).  Such an edge is skipped and counted when a slot is outside
+ *   [0, nimg), when the two slots are equal, or when a row is outside [0, count) of its slot.
+ *   Duplicate edges are harmless.
+ *  Components: the connected sets of two or more nodes; a component's label is its smallest id.
+ *  Tracks: a component with two nodes of one slot is inconsistent and dropped whole; a
+ *   consistent one with fewer than min_len nodes is dropped as short; the others are the tracks,
+ *   numbered in ascending label order.
+ * Outputs (device, caller-allocated for the worst case): track_offsets [nimg * cap / 2 + 1] (T + 1
+ * written: a CSR by track), obs_slot and obs_row [nimg * cap] (n_obs written; ascending slot
+ * within a track), node_track [nimg][cap] (the node's track id; -1: in no component, or beyond
+ * count; -2: its component is inconsistent; -3: short), out_n [6] = T, n_obs, inconsistent
+ * components, short components, skipped edges, the longest track.
+ * Integers only: two runs, and any order of the pairs or of the matches within a pair, write the
+ * same bytes.  Enqueued on `stream`, no synchronisation (growing the workspace, 36 to 52 bytes
+ * per node, frees buffers); one call at a time per context.  SFM_EINVAL: nimg or cap < 1,
+ * P < 0, nimg * cap > 2^30, min_len < 2, a null pointer (but keep; pairs, matches, nmatch when
+ * P == 0). */
+int32_t sfm_build_tracks_dev(sfm_ctx* ctx, const int32_t* count, int32_t nimg, int64_t cap, const int32_t* pairs,
+                             int32_t P, const int32_t* matches, const int32_t* nmatch, const uint8_t* keep,
+                             int32_t min_len, int32_t* track_offsets, int32_t* obs_slot, int32_t* obs_row,
+                             int32_t* node_track, int32_t* out_n, void* stream);
+
+/* Each track's 3-D point from all its views: CameraPose.triangulate_point (SFM.py:241-246)
+ * extended from 2 to V views.  track_offsets / obs_slot / obs_row: the CSR of
+ * sfm_build_tracks_dev with n_tracks tracks and n_obs observations (host values; offsets are
+ * clamped to [0, n_obs]); xy [nimg][cap][2] int32 the slot table's pixels; P [n_cam][12] row-major
+ * 3 x 4, one projection matrix per slot; cam_valid [n_cam] uint8 (optional; 0: the slot has no
+ * pose).  A view is valid when its slot is below min(nimg, n_cam), its row below cap and its
+ * camera valid.  Every valid view adds the rows x P[2] - P[0] and y P[2] - P[1] on raw pixel
+ * coordinates, in ascending slot order; X [n_tracks][3] (float64) is the right singular vector of
+ * the smallest singular value of the stacked rows divided by its fourth component, NaN with
+ * fewer than 2 valid views; out_views [n_tracks] the valid views.  The rows are folded one at a
+ * time into a 4 x 4 triangular factor by Givens rotations (A^T A is never formed), whose null
+ * vector comes from sfm_triangulate_dev's one-sided Jacobi; float64 without contraction, the
+ * same bits every run.  Enqueued on `stream`, not synchronised.  SFM_EINVAL: a negative count,
+ * nimg, cap or n_cam < 1, a null pointer (but cam_valid; outputs of an empty call). */
+int32_t sfm_triangulate_tracks_dev(sfm_ctx* ctx, const int32_t* track_offsets, const int32_t* obs_slot,
+                                   const int32_t* obs_row, int32_t n_tracks, int32_t n_obs, const int32_t* xy,
+                                   int32_t nimg, int64_t cap, const double* P, const uint8_t* cam_valid,
+                                   int32_t n_cam, double* X, int32_t* out_views, void* stream);
+
 /* sfm_ingest_rgb for B frames: rgb [B][H][W][3] uint8 -> gray [B][H2][W2] float32. */
 int32_t sfm_ingest_rgb_dev(sfm_ctx* ctx, const uint8_t* rgb, int32_t B, int32_t H, int32_t W,
                            int32_t H2, int32_t W2, float* gray, void* stream);

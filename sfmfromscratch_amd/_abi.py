@@ -28,6 +28,22 @@ SFM_MAX_LEVELS = 12
 SFM_BA_MAX_CAMERAS = 256          # sfm_bundle_adjust_dev: n_cam
 SFM_BA_MAX_POINTS = 1 << 24       # n_pts
 SFM_BA_MAX_OBSERVATIONS = 1 << 26  # M
+SFM_TRACKS_MAX_NODES = 1 << 30     # sfm_build_tracks_dev: nimg * cap
+
+_vp = ctypes.c_void_p
+# include/sfmfeat.h's feature-track calls as (restype, argtypes); device pointers are void*
+# (_native binds them; tests/test_tracks_cpu.py holds them against the header's prototypes)
+TRACK_SIGNATURES = {
+    # ctx, count, nimg, cap, pairs, P, matches, nmatch, keep, min_len, track_offsets, obs_slot,
+    # obs_row, node_track, out_n, stream
+    "sfm_build_tracks_dev": (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int64, _vp, ctypes.c_int32, _vp,
+                                              _vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # ctx, track_offsets, obs_slot, obs_row, n_tracks, n_obs, xy, nimg, cap, P, cam_valid, n_cam,
+    # X, out_views, stream
+    "sfm_triangulate_tracks_dev": (ctypes.c_int32, [_vp, _vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp,
+                                                    ctypes.c_int32, ctypes.c_int64, _vp, _vp, ctypes.c_int32, _vp,
+                                                    _vp, _vp]),
+}
 
 
 class SfmParams(ctypes.Structure):

@@ -77,6 +77,7 @@ SIGNATURES = {
     "sfm_bundle_adjust_dev": (ctypes.c_int32, [_vp, _vp, _vp, _vp, ctypes.c_int64, _vp, ctypes.c_int32, _vp, _vp,
                                                ctypes.c_int32, _vp, ctypes.c_double, ctypes.c_int32, _vp, _vp, _vp,
                                                _vp, _vp]),
+    **_abi.TRACK_SIGNATURES,  # sfm_build_tracks_dev, sfm_triangulate_tracks_dev
     "sfm_ingest_rgb_dev": (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                             ctypes.c_int32, ctypes.c_int32, _vp, _vp]),
     "sfm_extract_batch_dev": (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp,
@@ -442,6 +443,63 @@ class Context:
                        stream: int = 0):
         check(self.lib.sfm_match_prep_dev(self.handle, desc_ptr, count_ptr, nimg, cap, slot_lo, slot_n,
                                           stream or None), self.handle)
+
+    # -------- feature tracks (tensors, checked: the C ABI sees only addresses) --------
+    def _tensor_ptr(self, t, dtype: str, numel: int, what: str, optional: bool = False):
+        """The address of device tensor `t` for the C ABI: contiguous, of torch dtype `dtype`, on this
+        context's device, with at least `numel` elements; anything else raises ValueError."""
+        if t is None:
+            if optional:
+                return None
+            raise ValueError(f"{what} is required")
+        if not (hasattr(t, "data_ptr") and hasattr(t, "is_cuda")):
+            raise ValueError(f"{what} must be a device tensor")
+        if not t.is_cuda or (t.device.index or 0) != self.device:
+            raise ValueError(f"{what} must live on cuda:{self.device} (the context's device), not {t.device}")
+        if str(t.dtype) != "torch." + dtype:
+            raise ValueError(f"{what} must be {dtype}, not {t.dtype}")
+        if not t.is_contiguous():
+            raise ValueError(f"{what} must be contiguous")
+        if t.numel() < numel:
+            raise ValueError(f"{what} has {t.numel()} elements, fewer than {numel}")
+        return t.data_ptr()
+
+    def build_tracks_dev(self, count, cap: int, pairs, matches, nmatch, keep, min_len: int, track_offsets,
+                         obs_slot, obs_row, node_track, out_n, stream: int = 0):
+        """sfm_build_tracks_dev over device tensors (include/sfmfeat.h has the rule and the sizes)."""
+        nimg, cap = int(count.numel()) if hasattr(count, "numel") else 0, int(cap)
+        P = int(pairs.shape[0]) if pairs is not None and hasattr(pairs, "shape") and len(pairs.shape) == 2 else 0
+        if pairs is not None and tuple(getattr(pairs, "shape", ())) != (P, 2):
+            raise ValueError("pairs must be [P, 2]")
+        N = nimg * cap
+        tp = self._tensor_ptr
+        args = [tp(count, "int32", nimg, "count"), nimg, cap,
+                tp(pairs, "int32", 2 * P, "pairs", optional=P == 0), P,
+                tp(matches, "int32", 2 * P * cap, "matches", optional=P == 0),
+                tp(nmatch, "int32", P, "nmatch", optional=P == 0),
+                tp(keep, "uint8", P * cap, "keep", optional=True), int(min_len),
+                tp(track_offsets, "int32", N // 2 + 1, "track_offsets"), tp(obs_slot, "int32", N, "obs_slot"),
+                tp(obs_row, "int32", N, "obs_row"), tp(node_track, "int32", N, "node_track"),
+                tp(out_n, "int32", 6, "out_n")]
+        check(self.lib.sfm_build_tracks_dev(self.handle, *args, stream or None), self.handle)
+
+    def triangulate_tracks_dev(self, track_offsets, obs_slot, obs_row, n_tracks: int, n_obs: int, xy, P, cam_valid,
+                               X, out_views, stream: int = 0):
+        """sfm_triangulate_tracks_dev over device tensors: xy [nimg, cap, 2] int32, P [n_cam, 12]
+        (or [n_cam, 3, 4]) float64, cam_valid [n_cam] uint8 or None, X [n_tracks, 3], out_views."""
+        T, M = int(n_tracks), int(n_obs)
+        if len(getattr(xy, "shape", ())) != 3 or xy.shape[2] != 2:
+            raise ValueError("xy must be [nimg, cap, 2]")
+        nimg, cap = int(xy.shape[0]), int(xy.shape[1])
+        if not hasattr(P, "numel") or P.numel() % 12 or P.numel() == 0:
+            raise ValueError("P must hold n_cam >= 1 row-major 3 x 4 matrices")
+        n_cam = P.numel() // 12
+        tp = self._tensor_ptr
+        args = [tp(track_offsets, "int32", T + 1, "track_offsets"), tp(obs_slot, "int32", M, "obs_slot", M == 0),
+                tp(obs_row, "int32", M, "obs_row", M == 0), T, M, tp(xy, "int32", nimg * cap * 2, "xy"), nimg, cap,
+                tp(P, "float64", 12 * n_cam, "P"), tp(cam_valid, "uint8", n_cam, "cam_valid", optional=True), n_cam,
+                tp(X, "float64", 3 * T, "X", T == 0), tp(out_views, "int32", T, "out_views", T == 0)]
+        check(self.lib.sfm_triangulate_tracks_dev(self.handle, *args, stream or None), self.handle)
 
 
 def copy_wg(dst_ptr: int, src_ptr: int, nbytes: int, workgroups: int, stream: int = 0):

@@ -10,6 +10,7 @@
 //   api_pnp.hip      c->pnp (sample stream on the device, hypotheses, counts; the host streams
 //                    are c->ransac's cache)
 //   api_ba.hip       c->ba (the plan's lists, the linearisation, the Schur system, the LM state)
+//   api_tracks.hip   c->tracks (the union-find, the (root, slot) table, the scans' tile sums)
 //   api_profile.hip  c->prof   (stage events, Harris spans, the sfm_debug_* reads)
 #pragma once
 
@@ -188,6 +189,13 @@ struct BaWs {
   DevBuf st, Rt, Xs, cam_i, pt_cnt, pt_off, pt_list, pos, lin, e2, pts, lcam, Wm, Y, S, Spart, vec, nrm;
 };
 
+// Feature tracks (sfm_build_tracks_dev): per node parent, size, class and track id, the tracks'
+// nodes in fill order, the (root, slot) hash table and the scans' per-tile sums (tracks.h
+// TracksProblem).  One call at a time per context.
+struct TracksWs {
+  DevBuf parent, size, state, tid, tmp, hash, bsum;
+};
+
 struct sfm_ctx {
   CtxStreams s;  // (first: outlives the workspaces below)
   int device = 0;
@@ -210,6 +218,7 @@ struct sfm_ctx {
   RegistryWs registry;
   PnpWs pnp;
   BaWs ba;
+  TracksWs tracks;
   // the workspaces free their buffers after this body, the streams and events go last
   ~sfm_ctx() {
     (void)hipSetDevice(device);

@@ -1019,3 +1019,40 @@ class BundleAdjustment:
             if as_device:
                 return out_c, out_X
             return out_c.cpu().numpy(), out_X.cpu().numpy()
+
+
+# ---------------- N-view triangulation of feature tracks (tracks.hip) ----------------
+
+def triangulate_tracks(tracks, P, cam_valid=None, device: int = 0):
+    """Every track's 3-D point from all its views (include/sfmfeat.h sfm_triangulate_tracks_dev):
+    triangulate_point (SFM.py:241-246) with the two rows of every valid view stacked in ascending
+    slot order.  tracks: sequence.Tracks; P [n_cam, 3, 4] (or [n_cam, 12]), the projection matrix
+    of each slot; cam_valid (optional) [n_cam], zero / False where a slot has no pose.
+    -> (X [n_tracks, 3] float64, NaN with fewer than 2 valid views; views [n_tracks] int32).
+    numpy in, numpy out; a device tensor P gives device tensors.  The work runs on the tracks'
+    device (`device` is kept for symmetry with the other calls and must agree with it)."""
+    import torch
+    dev = tracks.xy.device
+    if (dev.index or 0) != int(device) and not _is_dev(P):
+        raise ValueError(f"triangulate_tracks: the tracks live on {dev}, not on cuda:{device}")
+    host = not _is_dev(P)
+    if int(np.prod(_shape_of(P))) % 12 or int(np.prod(_shape_of(P))) == 0:
+        raise ValueError("triangulate_tracks: P must be [n_cam, 3, 4]")
+    with torch.cuda.device(dev):
+        Pm = _f64_dev(P, (-1, 12), dev)
+        n_cam = int(Pm.shape[0])
+        cv = None
+        if cam_valid is not None:
+            cv = cam_valid if isinstance(cam_valid, torch.Tensor) else torch.from_numpy(np.asarray(cam_valid))
+            if cv.numel() != n_cam:
+                raise ValueError("triangulate_tracks: cam_valid must have one entry per camera")
+            cv = (cv.reshape(-1) != 0).to(device=dev, dtype=torch.uint8).contiguous()
+        T, M = tracks.n_tracks, tracks.n_obs
+        X = torch.empty((T, 3), dtype=torch.float64, device=dev)
+        views = torch.empty(T, dtype=torch.int32, device=dev)
+        ctx, stream = _structure_ctx(dev)
+        ctx.triangulate_tracks_dev(tracks.offsets_dev, tracks.obs_slot_dev, tracks.obs_row_dev, T, M, tracks.xy, Pm, cv,
+                                   X, views, stream)
+    if host:
+        return X.cpu().numpy(), views.cpu().numpy()
+    return X, views

@@ -258,3 +258,184 @@ def stage1(img_path: str, max_img: int, extractor_params: dict, match_threshold:
         all_matches[i1][i2] = Matches(mm, cc, p1, p2, single_K, single_K)
         all_matches[i2][i1] = Matches(mm, cc, p2, p1, single_K, single_K)
     return all_matches, cache
+
+
+# ---------------- feature tracks (tracks.hip) ----------------
+
+TRACK_STATS = ("n_tracks", "n_obs", "inconsistent", "short", "skipped_edges", "max_len")
+
+
+class Tracks:
+    """The feature tracks of a match graph (include/sfmfeat.h sfm_build_tracks_dev): a CSR by
+    track of (slot, row) observations, ascending by slot within a track, tracks in ascending
+    order of their smallest node id slot * cap + row.  The device tensors stay resident
+    (`offsets_dev`, `obs_slot_dev`, `obs_row_dev`, `node_track_dev`, `xy`: the slot table's
+    pixels); the numpy properties copy on first use, which synchronises."""
+
+    def __init__(self, offsets, obs_slot, obs_row, node_track, out_n, xy, min_len: int = 2):
+        self._offsets, self._obs_slot, self._obs_row = offsets, obs_slot, obs_row
+        self.node_track_dev, self._out_n, self.xy, self.min_len = node_track, out_n, xy, int(min_len)
+        self._host = {}
+
+    def _stat(self):
+        if "stats" not in self._host:
+            self._host["stats"] = self._out_n.cpu().numpy().astype(np.int64)
+        return self._host["stats"]
+
+    def _np(self, key, t):
+        if key not in self._host:
+            self._host[key] = t.cpu().numpy()
+        return self._host[key]
+
+    @property
+    def stats(self) -> dict:
+        """n_tracks, n_obs, inconsistent and short components, skipped edges, the longest track."""
+        return dict(zip(TRACK_STATS, (int(v) for v in self._stat())))
+
+    @property
+    def n_tracks(self) -> int:
+        return int(self._stat()[0])
+
+    @property
+    def n_obs(self) -> int:
+        return int(self._stat()[1])
+
+    @property
+    def offsets_dev(self):
+        return self._offsets[: self.n_tracks + 1]
+
+    @property
+    def obs_slot_dev(self):
+        return self._obs_slot[: self.n_obs]
+
+    @property
+    def obs_row_dev(self):
+        return self._obs_row[: self.n_obs]
+
+    @property
+    def offsets(self) -> np.ndarray:
+        return self._np("offsets", self.offsets_dev)
+
+    @property
+    def obs_slot(self) -> np.ndarray:
+        return self._np("obs_slot", self.obs_slot_dev)
+
+    @property
+    def obs_row(self) -> np.ndarray:
+        return self._np("obs_row", self.obs_row_dev)
+
+    @property
+    def node_track(self) -> np.ndarray:
+        return self._np("node_track", self.node_track_dev)
+
+    @property
+    def obs_xy(self) -> np.ndarray:
+        """[n_obs, 2] int32: the pixel of every observation."""
+        if "obs_xy" not in self._host:
+            s, r = self.obs_slot_dev.long(), self.obs_row_dev.long()
+            self._host["obs_xy"] = self.xy[s, r].cpu().numpy()
+        return self._host["obs_xy"]
+
+    def ba_inputs(self):
+        """(camera_indices [n_obs], point_indices [n_obs], points_2d [n_obs, 2]) as
+        pose.BundleAdjustment and PointRegistry.prepare_for_ba take them: the camera of an
+        observation is its slot, its point is its track."""
+        point_indices = np.repeat(np.arange(self.n_tracks, dtype=np.int64), np.diff(self.offsets))
+        return self.obs_slot.astype(np.int64), point_indices, self.obs_xy.astype(np.float64)
+
+    def save(self, path: str) -> None:
+        """The tracks as one .npz (the style of save_matches), format tag sfmfeat-tracks-v1."""
+        np.savez(path, format=np.array("sfmfeat-tracks-v1"), offsets=self.offsets, obs_slot=self.obs_slot,
+                 obs_row=self.obs_row, node_track=self.node_track, obs_xy=self.obs_xy, stats=self._stat(),
+                 min_len=np.array(self.min_len, np.int64))
+
+    @classmethod
+    def load(cls, path: str, device: int = 0) -> "Tracks":
+        """Tracks as written by `save`, uploaded to `device`; `xy` holds the saved observations'
+        pixels and zeros elsewhere."""
+        import torch
+        with np.load(path, allow_pickle=False) as z:
+            if str(z["format"]) != "sfmfeat-tracks-v1":
+                raise ValueError(f"{path}: not an sfmfeat track file")
+            off, s, r, nt, oxy, st, ml = (z[k] for k in ("offsets", "obs_slot", "obs_row", "node_track", "obs_xy",
+                                                          "stats", "min_len"))
+        dev = torch.device("cuda", device)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.int32)).to(dev)  # noqa: E731
+        xy = torch.zeros(tuple(nt.shape) + (2,), dtype=torch.int32, device=dev)
+        if len(s):
+            xy[up(s).long(), up(r).long()] = up(oxy)
+        return cls(up(off), up(s), up(r), up(nt), up(st), xy, int(ml))
+
+
+def _padded_matches(torch, matches, keep, P, cap, dev):
+    """The host list of match_schedule (and an optional list of per-pair masks) in the padded
+    device layout of sfm_match_pairs_dev: matches [P, cap, 2], nmatch [P], keep [P, cap] or None."""
+    if len(matches) != P:
+        raise ValueError("build_tracks: one (matches, confidences) entry per pair")
+    mm = np.zeros((max(P, 1), cap, 2), np.int32)
+    nm = np.zeros(max(P, 1), np.int32)
+    kk = None if keep is None else np.zeros((max(P, 1), cap), np.uint8)
+    for p, entry in enumerate(matches):
+        m = np.asarray(entry[0] if isinstance(entry, (tuple, list)) else entry).reshape(-1, 2)
+        if len(m) > cap:
+            raise ValueError(f"build_tracks: pair {p} has {len(m)} matches, more than the table's capacity {cap}")
+        mm[p, :len(m)] = m
+        nm[p] = len(m)
+        if kk is not None:
+            k = np.asarray(keep[p]).reshape(-1)
+            if len(k) != len(m):
+                raise ValueError(f"build_tracks: keep[{p}] must have one entry per match of pair {p}")
+            kk[p, :len(m)] = k != 0
+    return (torch.from_numpy(mm).to(dev), torch.from_numpy(nm).to(dev),
+            None if kk is None else torch.from_numpy(kk).to(dev))
+
+
+def build_tracks(cache, pairs, matches, keep=None, min_len: int = 2) -> Tracks:
+    """Feature tracks of the matches of a pair schedule: the connected components of the graph
+    whose nodes are the table's keypoints and whose edges are the matches; a component that visits
+    one frame twice is dropped whole, one with fewer than `min_len` keypoints too
+    (include/sfmfeat.h sfm_build_tracks_dev has the rule in full).
+
+    cache: the FeatureCache the matches came from (or its SlotTable).  pairs [P, 2].  matches:
+    the device triple of BatchMatcher.match (matches [P, cap, 2], conf, nmatch), used in place, or
+    the host list match_schedule returns, uploaded into that layout.  keep (optional): which
+    matches count — [P, cap] (numpy or a device tensor, non-zero = keep), or with a host list one
+    mask per pair; this is where a caller's geometric verification comes in, none is built in.
+    Enqueued on torch's current stream; nothing synchronises until a host property is read."""
+    import torch
+    from . import _abi
+    from ._native import context_for
+    slots = getattr(cache, "slots", cache)
+    dev = slots.xy.device
+    nimg, cap = int(slots.count.numel()), int(slots.xy.shape[1])
+    extractor = getattr(cache, "extractor", None)
+    ctx = extractor.ctx if extractor is not None else \
+        context_for(_abi.params_from_dict({}, _abi.SFM_MODE_NAIVE), dev.index or 0)
+    if isinstance(pairs, torch.Tensor):
+        pt = pairs.to(device=dev, dtype=torch.int32).reshape(-1, 2).contiguous()
+    else:
+        pt = torch.from_numpy(np.ascontiguousarray(np.asarray(pairs).reshape(-1, 2), np.int32)).to(dev)
+    P = int(pt.shape[0])
+    with torch.cuda.device(dev):
+        if len(matches) == 3 and isinstance(matches[0], torch.Tensor):
+            mm, nm = matches[0], matches[2]
+            if mm.dim() != 3 or tuple(mm.shape[1:]) != (cap, 2) or int(mm.shape[0]) < P:
+                raise ValueError(f"build_tracks: matches must be [P, {cap}, 2] for the table's capacity")
+            kk = None
+            if keep is not None:
+                kk = keep if isinstance(keep, torch.Tensor) else torch.from_numpy(np.asarray(keep))
+                if tuple(kk.shape) != (int(mm.shape[0]), cap) and tuple(kk.shape) != (P, cap):
+                    raise ValueError(f"build_tracks: keep must be [P, {cap}]")
+                kk = (kk != 0).to(device=dev, dtype=torch.uint8).contiguous()
+        else:
+            mm, nm, kk = _padded_matches(torch, matches, keep, P, cap, dev)
+        N = nimg * cap
+        offsets = torch.empty(N // 2 + 1, dtype=torch.int32, device=dev)
+        obs_slot = torch.empty(N, dtype=torch.int32, device=dev)
+        obs_row = torch.empty(N, dtype=torch.int32, device=dev)
+        node_track = torch.empty((nimg, cap), dtype=torch.int32, device=dev)
+        out_n = torch.empty(6, dtype=torch.int32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        ctx.build_tracks_dev(slots.count, cap, pt, mm, nm, kk, int(min_len), offsets, obs_slot, obs_row, node_track,
+                             out_n, stream)
+    return Tracks(offsets, obs_slot, obs_row, node_track, out_n, slots.xy, min_len)
