@@ -136,6 +136,14 @@ int32_t sfm_extract(sfm_ctx* ctx, const float* img, int32_t H, int32_t W, int64_
  *   matches: k x 2 int64 [row in d1, row in d2]; conf: k float32 nndr
  *   sorted by (conf ascending, row ascending).  cap >= n1 always suffices.
  * Returns SFM_EINDEX when n2 < 2 (the reference raises IndexError at :42).
+ *
+ * Domain (this call, sfm_match_pairs_dev and sfm_match_pairs_prepped_dev): any finite float32
+ * tables whose reference distances sqrt(sum((a - b)^2)) in float32 are all finite — not only
+ * unit-norm descriptors.  Results equal the reference on all of them.  The MFMA prefilter
+ * covers elements with |x| * 2^8 finite in float16 (|x| < 255.9375); a row holding a larger
+ * element, and every query row matched against an image that holds such a row, is computed
+ * exactly over all targets instead (slower, same results).  Tables with non-finite elements
+ * are unspecified: the reference's own result then depends on its unstable sort.
  */
 int32_t sfm_match(sfm_ctx* ctx, const float* d1, int64_t n1, const float* d2, int64_t n2,
                   float ratio, int64_t* matches, float* conf, int64_t cap, int64_t* k_out);
@@ -646,6 +654,36 @@ float sfm_debug_harris_stamps(int32_t device, int32_t abl, int32_t B, int32_t H,
  * region, after the DMA issue; row 40: start clock, start / end realtime, pair | stages << 32),
  * then u64 [1024 workgroups][4]: start / end realtime, __smid(), pair | row0 << 32. */
 int64_t sfm_debug_match_stamps(uint64_t* out, int64_t cap);
+
+/* The matcher's intermediate state, copied out of the context's workspaces (both calls
+ * synchronise the device; host outputs; SFM_ESTATE on a SFMFEAT_MATCH_DIRECT context).
+ *
+ * sfm_debug_match_operands: the operands of slot `slot` of the table last prepped
+ * (sfm_match_prep_dev, or the prep inside sfm_match / sfm_match_pairs_dev) or written by a fused
+ * extraction on this context.  rows must be that table's capP (cap rounded up to 128, else
+ * SFM_EINVAL).  hi, lo [rows][128]: the float16 bit patterns of f16(x * 2^8) and
+ * f16((x * 2^8 - hi) * 2^11); norm2, rnorm [rows]: float32 of the squared norm summed in
+ * double, and of its square root (rows at or beyond the slot's count: norm2 = +inf); pmax
+ * [rows / 16][2]: the (norm2, rnorm) maxima of each block of 16 rows.  A row with an element
+ * outside the float16 range has hi = lo = 0 and rnorm = +inf.  SFM_ESTATE when the context
+ * holds no operands for that slot (no prep or fused extraction yet, or the slot is outside
+ * the prepped table / the extraction's batch).
+ *
+ * sfm_debug_match_windows: the prefilter's windows of pair `pair` of the last sfm_match /
+ * sfm_match_pairs*_dev call on this context, for its first `rows` query rows (1 <= rows <= that
+ * call's cap).  cand_n [rows]: the two half-list counts (low / high 16 bits; the appends a
+ * half-list saw, which may exceed its 128 entries: then, or when the count word is 0x7fff — the
+ * row's error bound (2E, as the sweep carries it) was not finite —, the row was computed exactly
+ * over all targets);
+ * cand_thr [rows]: the row's final threshold b2~ + 2E; cand [rows][256]: the list words, half
+ * h at [128 h ...): target index in the low 16 bits, d~ rounded down to bfloat16 in the high
+ * 16.  Rows at or beyond the pair's first count, and every row of a pair whose second image is
+ * empty, are not written.  SFM_ESTATE when that call ran as more than one sub-launch (the
+ * workspaces then hold the last one only) or no call was made; SFM_EINVAL for pair outside it. */
+int32_t sfm_debug_match_operands(sfm_ctx* ctx, int32_t slot, int64_t rows, uint16_t* hi, uint16_t* lo,
+                                 float* norm2, float* rnorm, float* pmax);
+int32_t sfm_debug_match_windows(sfm_ctx* ctx, int32_t pair, int64_t rows, int32_t* cand_n, float* cand_thr,
+                                uint32_t* cand);
 
 /* Exchange emulation for a single-GPU rehearsal of the multi-GPU job (bench.py
  * --emulate-exchange): copy `bytes` from src to dst (device pointers, 16-B aligned) on

@@ -46,6 +46,18 @@ TRACK_SIGNATURES = {
 }
 
 
+# include/sfmfeat.h's read-backs of the matcher's intermediate state (host pointers as void*;
+# tests/test_abi_cpu.py holds them against the header's prototypes)
+MATCH_DEBUG_SIGNATURES = {
+    # ctx, slot, rows, hi, lo, norm2, rnorm, pmax
+    "sfm_debug_match_operands": (ctypes.c_int32, [_vp, ctypes.c_int32, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp]),
+    # ctx, pair, rows, cand_n, cand_thr, cand
+    "sfm_debug_match_windows": (ctypes.c_int32, [_vp, ctypes.c_int32, ctypes.c_int64, _vp, _vp, _vp]),
+}
+MATCH_CAND_CAP = 256   # list words per query row (two half-lists of 128)
+MATCH_PREP_ROWS = 16   # rows per block of the operands' (norm2, rnorm) maxima
+
+
 class SfmParams(ctypes.Structure):
     _fields_ = [
         ("mode", ctypes.c_int32),

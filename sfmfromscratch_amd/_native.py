@@ -106,6 +106,7 @@ SIGNATURES = {
     "sfm_debug_harris_stamps": (ctypes.c_float, [ctypes.c_int32] * 6 + [ctypes.c_void_p, ctypes.c_int64]),
     "sfm_debug_match_stamps": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int64]),
     "sfm_debug_select_stats": (ctypes.c_int32, [_vp, _i32p, _i32p]),
+    **_abi.MATCH_DEBUG_SIGNATURES,  # sfm_debug_match_operands, sfm_debug_match_windows
     "sfm_copy_wg": (ctypes.c_int32, [_vp, _vp, ctypes.c_int64, ctypes.c_int32, _vp]),
     "sfm_dist_unique_id": (ctypes.c_int32, [_u8p]),
     "sfm_dist_create": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _u8p, ctypes.POINTER(_vp)]),
@@ -443,6 +444,33 @@ class Context:
                        stream: int = 0):
         check(self.lib.sfm_match_prep_dev(self.handle, desc_ptr, count_ptr, nimg, cap, slot_lo, slot_n,
                                           stream or None), self.handle)
+
+    def match_operands(self, slot: int, cap: int):
+        """sfm_debug_match_operands of one slot of the table last prepped / fused on this context
+        (capacity `cap`) -> hi, lo [capP, 128] uint16 (float16 bits), norm2, rnorm [capP] float32,
+        pmax [capP / 16, 2] float32."""
+        capP = (int(cap) + 127) // 128 * 128
+        hi = np.empty((capP, 128), np.uint16)
+        lo = np.empty((capP, 128), np.uint16)
+        norm2 = np.empty(capP, np.float32)
+        rnorm = np.empty(capP, np.float32)
+        pmax = np.empty((capP // _abi.MATCH_PREP_ROWS, 2), np.float32)
+        check(self.lib.sfm_debug_match_operands(self.handle, int(slot), capP, hi.ctypes.data, lo.ctypes.data,
+                                                norm2.ctypes.data, rnorm.ctypes.data, pmax.ctypes.data),
+              self.handle)
+        return hi, lo, norm2, rnorm, pmax
+
+    def match_windows(self, pair: int, rows: int):
+        """sfm_debug_match_windows of pair `pair` of the last match call on this context -> cand_n
+        [rows] int32 (half-list counts, low / high 16 bits), cand_thr [rows] float32, cand
+        [rows, 256] uint32 (target index | bf16-rounded-down d~ << 16)."""
+        rows = int(rows)
+        cn = np.empty(max(rows, 1), np.int32)
+        ct = np.empty(max(rows, 1), np.float32)
+        cd = np.empty((max(rows, 1), _abi.MATCH_CAND_CAP), np.uint32)
+        check(self.lib.sfm_debug_match_windows(self.handle, int(pair), rows, cn.ctypes.data, ct.ctypes.data,
+                                               cd.ctypes.data), self.handle)
+        return cn, ct, cd
 
     # -------- feature tracks (tensors, checked: the C ABI sees only addresses) --------
     def _tensor_ptr(self, t, dtype: str, numel: int, what: str, optional: bool = False):

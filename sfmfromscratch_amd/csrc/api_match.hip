@@ -130,6 +130,9 @@ int match_impl(sfm_ctx* c, const float* desc, const int32_t* count, int nimg, in
   }
   const int64_t capP = operand_rows(c, cap);
   const bool skip_sweep = (extract_switches().skip & 8) != 0;  // SFMFEAT_SKIP: all but the first sub-launch
+  m.last_P = P;
+  m.last_cap = cap;
+  m.last_subs = (P + Pmax - 1) / Pmax;
   for (int p0 = 0; p0 < P; p0 += Pmax, ++m.calls) {
     const int Pn = std::min(Pmax, P - p0);
     const int32_t* pr = pairs + 2 * (int64_t)p0;
@@ -248,6 +251,45 @@ int32_t sfm_match_pairs_prepped_dev(sfm_ctx* c, const float* desc, const int32_t
   HIPCHK(c, hipSetDevice(c->device));
   return match_impl(c, desc, count, nimg, cap, pairs, P, ratio, matches, conf, nmatch, (hipStream_t)stream,
                     false);
+}
+
+int32_t sfm_debug_match_operands(sfm_ctx* c, int32_t slot, int64_t rows, uint16_t* hi, uint16_t* lo, float* norm2,
+                                 float* rnorm, float* pmax) {
+  if (!c || !hi || !lo || !norm2 || !rnorm || !pmax || slot < 0) return SFM_EINVAL;
+  MatchOperandsWs& o = c->match.ops;
+  if (c->match.direct) return set_err(c, SFM_ESTATE, "the direct matcher has no split-f16 operands");
+  if (o.cap < 1 || !(slot < o.fused_B || slot < o.prep_nimg))
+    return set_err(c, SFM_ESTATE, "no matcher operands for that slot on this context");
+  const int64_t capP = operand_rows(c, o.cap);
+  if (rows != capP) return set_err(c, SFM_EINVAL, "rows must be the table's capacity rounded up to 128");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipDeviceSynchronize());
+  const size_t r0 = (size_t)slot * capP, nb = (size_t)capP;
+  HIPCHK(c, hipMemcpy(hi, as<_Float16>(o.hi) + r0 * 128, nb * 128 * 2, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(lo, as<_Float16>(o.lo) + r0 * 128, nb * 128 * 2, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(norm2, as<float>(o.norm2) + r0, nb * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(rnorm, as<float>(o.rnorm) + r0, nb * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(pmax, as<char>(o.imgmax) + (size_t)slot * match_pmax_bytes(capP), match_pmax_bytes(capP),
+                      hipMemcpyDeviceToHost));
+  return SFM_OK;
+}
+
+int32_t sfm_debug_match_windows(sfm_ctx* c, int32_t pair, int64_t rows, int32_t* cand_n, float* cand_thr,
+                                uint32_t* cand) {
+  if (!c || !cand_n || !cand_thr || !cand || pair < 0 || rows < 1) return SFM_EINVAL;
+  MatchWs& m = c->match;
+  if (m.direct) return set_err(c, SFM_ESTATE, "the direct matcher keeps no windows");
+  if (m.last_subs != 1)
+    return set_err(c, SFM_ESTATE, m.last_subs ? "the last match call ran as more than one sub-launch"
+                                              : "no match call on this context yet");
+  if (pair >= m.last_P || rows > m.last_cap) return set_err(c, SFM_EINVAL, "pair or rows outside the last match call");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipDeviceSynchronize());
+  const size_t r0 = (size_t)pair * (size_t)m.last_cap, n = (size_t)rows;
+  HIPCHK(c, hipMemcpy(cand_n, as<int32_t>(m.candn) + r0, n * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(cand_thr, as<float>(m.candt) + r0, n * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(cand, as<uint32_t>(m.cand) + r0 * kMatchCandCap, n * kMatchCandCap * 4, hipMemcpyDeviceToHost));
+  return SFM_OK;
 }
 
 }  // extern "C"

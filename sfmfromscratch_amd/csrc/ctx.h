@@ -137,6 +137,9 @@ struct MatchWs {
   // sub-launch at 256 admitted targets per row, configs[2]'s 4,096-pair calls in three)
   size_t budget = (size_t)4096 << 20;
   int64_t calls = 0;  // match sub-launches (SFMFEAT_SKIP leaves the first one whole)
+  // the last match call: pairs, capacity and sub-launches (sfm_debug_match_windows)
+  int last_P = 0, last_subs = 0;
+  int64_t last_cap = 0;
 };
 
 // ingest (sfm_ingest_rgb*): resample tables for the cached (W -> W2, H -> H2) and the RGB temp

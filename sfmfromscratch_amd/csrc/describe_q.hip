@@ -566,8 +566,14 @@ __global__ void __launch_bounds__(64) k_describe_q(const float* __restrict__ lvl
   dst[0] = make_float4(o[0], o[1], o[2], o[3]);
   dst[1] = make_float4(o[4], o[5], o[6], o[7]);
   if (mo.hi != nullptr) {
-    // the matcher's operands of this row (k_match_prep's arithmetic: the same hi / lo of each
-    // element; the squared norm summed in double over the row's 16 lanes)
+    // the matcher's operands of this row: the same hi / lo bits as k_match_prep for each
+    // element.  The squared norm is summed in double in another order (8 elements per lane,
+    // then a 16-lane butterfly; k_match_prep: 2 per lane, then a 64-lane butterfly), so
+    // norm2 / rnorm could differ from k_match_prep's by one float32 ulp where the two double
+    // sums straddle a rounding boundary; they had the same bits on every row tested (872 rows,
+    // tests/test_gpu_match_domain.py, which allows that one ulp), and E's 4e-6 (|a|^2 + |b|^2)
+    // term covers 33 ulp of each norm.  No out-of-f16-range flag as in k_match_prep: RootSIFT
+    // elements are at most 1.
     const int64_t r = off0 + kpi, mr = (int64_t)b * mo.capP + r;
     typedef _Float16 h8 __attribute__((ext_vector_type(8)));
     h8 hh, ll;

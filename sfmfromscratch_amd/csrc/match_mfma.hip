@@ -16,7 +16,8 @@
 //      reference's exact float32 pairwise order (8 accumulators), (distance, index) top-2,
 //      ratio test;
 //   3. k_match_overflow: rows whose list overflowed (runs of near-identical target
-//      descriptors) recomputed exactly over every target.
+//      descriptors), and rows whose bound E is not finite (an element outside the f16 range
+//      in the row or in the target image, k_match_prep), recomputed exactly over every target.
 #include <stdlib.h>
 
 #include <type_traits>
@@ -64,20 +65,32 @@ __global__ void __launch_bounds__(256) k_match_prep(const float* __restrict__ de
       a1 = src[lane + 64];
     }
     float v[2] = {a0, a1};
+    _Float16 h[2], l[2];
     double s = 0.0;
+    bool out = false;  // an element whose scaled value is not finite in f16 (|x| >= 255.9375)
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       float x = v[q] * kScale;
-      _Float16 h = (_Float16)x;
-      float r = (x - (float)h) * kLoScale;  // exact difference, exact power-of-two scaling
-      hi[o + lane + 64 * q] = h;
-      lo[o + lane + 64 * q] = (_Float16)r;
+      h[q] = (_Float16)x;
+      float r = (x - (float)h[q]) * kLoScale;  // exact difference, exact power-of-two scaling
+      l[q] = (_Float16)r;
+      out = out || !(fabsf((float)h[q]) <= 65504.0f);
       s += (double)v[q] * (double)v[q];
+    }
+    // such a row has no f16 operands: zero hi / lo (no inf or NaN reaches the MFMAs) and a +inf
+    // norm, which makes E non-finite for this row as a query and, through the block maximum,
+    // for every query row of a pair whose target image holds it: the sweep hands those rows to
+    // k_match_overflow (exact over all targets)
+    const bool flagged = __any(out);
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      hi[o + lane + 64 * q] = flagged ? (_Float16)0.0f : h[q];
+      lo[o + lane + 64 * q] = flagged ? (_Float16)0.0f : l[q];
     }
     for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
     if (lane == 0) {
       float n2 = (float)s;
-      float rn = (float)sqrt(s);
+      float rn = flagged ? INFINITY : (float)sqrt(s);
       // padding rows: +inf squared norm, so their approximate distance is +inf and the
       // sweep needs no bounds checks (never admitted, never in the top 2)
       norm2[(int64_t)img * capP + row] = row < n ? n2 : INFINITY;
@@ -768,10 +781,14 @@ __global__ void __launch_bounds__(64 * sweep_waves(STAGE), STAGE == 3 ? 2 : 1) k
   const float ob1 = other_half(b1), ob2 = other_half(b2);
   const float thr_final = fminf(fminf(fmaxf(b1, ob1), fminf(b2, ob2)) + E2, thr_w);
   const int ocnt = other_half(cnt);
+  // a non-finite bound (k_match_prep flagged this row, or a row of the target image: an element
+  // outside the f16 range; or the norms overflow float32): the window proves nothing, so the
+  // row takes an over-cap count (the re-rank skips it) and the exact kernel
+  const bool unbounded = !(E2 <= 3.0e38f);  // E2 = 2E, live to the end anyway
   if (live && half == 0) {
     cand_thr[(int64_t)p * max_rows + qi] = thr_final;
-    cand_n[(int64_t)p * max_rows + qi] = cnt | (ocnt << 16);  // n2 < 2^16 (kMaxMatchRows)
-    if (cnt > kHalfCap || ocnt > kHalfCap) {  // a list overflowed: exact over every target instead
+    cand_n[(int64_t)p * max_rows + qi] = unbounded ? 0x7fff : cnt | (ocnt << 16);  // n2 < 2^16 (kMaxMatchRows)
+    if (cnt > kHalfCap || ocnt > kHalfCap || unbounded) {  // exact over every target instead
       const int k = atomicAdd(ovf_count, 1);
       ovf_list[k] = make_int2(p, qi);
     }

@@ -33,6 +33,30 @@ def test_library_exports_every_header_symbol():
         assert n in _native.SIGNATURES, f"{n} not bound in _native.SIGNATURES"
 
 
+C_TYPES = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float,
+           "double": ctypes.c_double}
+
+
+def header_prototype(name):
+    """(restype, argtypes) of `name` as include/sfmfeat.h declares it; every pointer is void*."""
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    m = re.search(r"(\w+)\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
+    assert m, f"{name} is not declared in include/sfmfeat.h"
+    args = [ctypes.c_void_p if "*" in a else C_TYPES[a.replace("const ", "").split()[0]]
+            for a in (a.strip() for a in m.group(2).split(","))]
+    return C_TYPES[m.group(1)], args
+
+
+@pytest.mark.parametrize("name", ["sfm_debug_match_operands", "sfm_debug_match_windows"])
+def test_abi_declares_the_matcher_read_backs_with_the_headers_signatures(name):
+    res, args = header_prototype(name)
+    assert _abi.MATCH_DEBUG_SIGNATURES[name] == (res, args)
+    assert _native.SIGNATURES[name] == (res, args)
+    fn = getattr(_native.load_library(), name)
+    # argument errors come back before any device call
+    assert fn(*[None if a is ctypes.c_void_p else 0 for a in args]) == _abi.SFM_EINVAL
+
+
 def test_struct_layout_matches_header(tmp_path):
     """ctypes mirror == the C compiler's layout of sfm_params (offsets and size)."""
     import subprocess
