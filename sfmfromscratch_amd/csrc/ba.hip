@@ -4,7 +4,7 @@
 // is not pinned: the minimum is.
 //
 // Once per call (the plan):
-// * k_ba_init: R = Rodrigues(camera_params) (k_total_reproj's closed form), t and X copied into
+// * k_ba_init: R = Rodrigues(camera_params) (linalg3.h rodrigues), t and X copied into
 //   slot 0 of the two-slot state; the LM state (lambda, counters) reset.
 // * k_ba_count / k_ba_scan / k_ba_fill_pt / k_ba_sort_pt: per-point observation lists as offsets
 //   + observation indices.  Integer atomics count and hand out slots; every list is then sorted
@@ -27,9 +27,9 @@
 // * k_ba_update: the candidate state (other slot): dX_j = -V*_j^-1 (g_j + W_j^T d_c),
 //   R <- exp([d omega]x) R, t <- t + d t; per-row |d|^2 and |params|^2.
 // * k_ba_resid: squared residual per observation at the candidate.
-// * k_ba_decide, one workgroup: the candidate cost and the two norms by k_total_mean's fixed
-//   tree; thread 0 accepts or rejects, moves lambda, the counters, the slot and `done`.
-// Finally k_ba_finish: R -> principal Rodrigues vector (pose.rodrigues's closed form); rows
+// * k_ba_decide, one workgroup: the candidate cost and the two norms by block_sum256_tree;
+//   thread 0 accepts or rejects, moves lambda, the counters, the slot and `done`.
+// Finally k_ba_finish: R -> principal Rodrigues vector (linalg3.h rodrigues_inv); rows
 // that never moved return their input bits.
 // No cooperative launch, no grid barrier, no wait on memory: every loop is bounded by a size
 // passed in.  Float64 throughout; -ffp-contract=off.
@@ -38,86 +38,15 @@
 
 #include <algorithm>
 
+#include "f64_dev.h"
 #include "kernels.h"
+#include "linalg3.h"
 
 namespace sfm {
 
 constexpr int kBaThreads = 256;
 constexpr int kBaSolveThreads = 1024;
 constexpr int kBaLin = 20;  // per observation: r (2), J_c rows (6 + 6), J_p rows (3 + 3)
-
-SFM_DEV bool ba_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }  // false for NaN
-SFM_DEV int ba_clamp(int v, int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
-
-// cv2.Rodrigues, vector -> matrix: identity below DBL_EPSILON (k_total_reproj's closed form)
-SFM_DEV void ba_rodrigues(double r0, double r1, double r2, double (&R)[9]) {
-  const double th = sqrt((r0 * r0 + r1 * r1) + r2 * r2);
-  R[0] = 1.0, R[1] = 0.0, R[2] = 0.0, R[3] = 0.0, R[4] = 1.0, R[5] = 0.0, R[6] = 0.0, R[7] = 0.0, R[8] = 1.0;
-  if (!(th < 2.220446049250313e-16)) {
-    const double cs = cos(th), sn = sin(th), c1 = 1.0 - cs;
-    const double kx = r0 / th, ky = r1 / th, kz = r2 / th;
-    R[0] = cs + c1 * kx * kx;
-    R[1] = c1 * kx * ky - sn * kz;
-    R[2] = c1 * kx * kz + sn * ky;
-    R[3] = c1 * kx * ky + sn * kz;
-    R[4] = cs + c1 * ky * ky;
-    R[5] = c1 * ky * kz - sn * kx;
-    R[6] = c1 * kx * kz - sn * ky;
-    R[7] = c1 * ky * kz + sn * kx;
-    R[8] = cs + c1 * kz * kz;
-  }
-}
-
-// matrix -> principal vector, as pose.rodrigues: the antisymmetric part up to theta = pi / 2,
-// beyond it the axis from the symmetric part
-SFM_DEV void ba_rodrigues_inv(const double (&R)[9], double (&r)[3]) {
-  const double v[3] = {(R[7] - R[5]) / 2.0, (R[2] - R[6]) / 2.0, (R[3] - R[1]) / 2.0};
-  const double s = sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
-  const double c = (((R[0] + R[4]) + R[8]) - 1.0) / 2.0;
-  const double th = atan2(s, c);
-  if (c >= 0) {
-    const double f = s == 0 ? 1.0 : th / s;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) r[k] = s == 0 ? v[k] : v[k] * f;
-    return;
-  }
-  const double dg[3] = {R[0], R[4], R[8]};
-  double k2[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) k2[k] = fmax((dg[k] - c) / (1.0 - c), 0.0);
-  const int best = k2[0] >= k2[1] ? (k2[0] >= k2[2] ? 0 : 2) : (k2[1] >= k2[2] ? 1 : 2);  // the first maximum
-  double kk[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    if (i != best) continue;
-    kk[i] = v[i] < 0 ? -sqrt(k2[i]) : sqrt(k2[i]);
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-      if (j != i) kk[j] = (R[3 * i + j] + R[3 * j + i]) / 2.0 / ((1.0 - c) * kk[i]);
-  }
-  const double nk = sqrt((kk[0] * kk[0] + kk[1] * kk[1]) + kk[2] * kk[2]);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) r[k] = kk[k] / nk * th;
-}
-
-// the fixed tree of k_total_mean over blockDim.x == 256 threads; every thread gets the sum
-SFM_DEV double ba_block_sum(double v, double* s_red) {
-  const int tid = threadIdx.x;
-  __syncthreads();  // the previous sum has been read
-  s_red[tid] = v;
-  __syncthreads();
-  for (int off = kBaThreads / 2; off >= 1; off >>= 1) {
-    if (tid < off) s_red[tid] += s_red[tid + off];
-    __syncthreads();
-  }
-  return s_red[0];
-}
-
-SFM_DEV double ba_wave_sum(double v) {  // every lane gets the same bits
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
 
 // ---------------- the plan ----------------
 
@@ -137,7 +66,7 @@ __global__ void __launch_bounds__(kBaThreads) k_ba_init(BaProblem p) {
     const int c = (int)(i - p.n_pts);
     const double* cp = p.cams_in + 6 * c;
     double R[9];
-    ba_rodrigues(cp[0], cp[1], cp[2], R);
+    rodrigues(cp[0], cp[1], cp[2], R);
     double* o = p.Rt + 12 * c;
 #pragma unroll
     for (int k = 0; k < 9; ++k) o[k] = R[k];
@@ -150,8 +79,8 @@ __global__ void __launch_bounds__(kBaThreads) k_ba_init(BaProblem p) {
 __global__ void __launch_bounds__(kBaThreads) k_ba_count(BaProblem p) {
   const int o = blockIdx.x * kBaThreads + threadIdx.x;
   if (o >= p.M) return;
-  atomicAdd(&p.pt_cnt[ba_clamp(p.pt_idx[o], p.n_pts)], 1);
-  atomicAdd(&p.cam_cnt[ba_clamp(p.cam_idx[o], p.n_cam)], 1);
+  atomicAdd(&p.pt_cnt[clamp_index(p.pt_idx[o], p.n_pts)], 1);
+  atomicAdd(&p.cam_cnt[clamp_index(p.cam_idx[o], p.n_cam)], 1);
 }
 
 // one workgroup: exclusive scans of both counts; pt_cnt becomes the fill cursor
@@ -184,7 +113,7 @@ __global__ void __launch_bounds__(kBaThreads) k_ba_scan(BaProblem p) {
 __global__ void __launch_bounds__(kBaThreads) k_ba_fill_pt(BaProblem p) {
   const int o = blockIdx.x * kBaThreads + threadIdx.x;
   if (o >= p.M) return;
-  const int j = ba_clamp(p.pt_idx[o], p.n_pts);
+  const int j = clamp_index(p.pt_idx[o], p.n_pts);
   const int slot = atomicAdd(&p.pt_cnt[j], 1);
   const int k = p.pt_off[j + 1] - p.pt_off[j];
   if (slot < k) p.pt_list[p.pt_off[j] + slot] = o;  // (always: the counts are this launch's)
@@ -215,7 +144,7 @@ __global__ void __launch_bounds__(kBaThreads) k_ba_fill_cam(BaProblem p) {
   const uint32_t end = (uint32_t)p.cam_off[c + 1];
   for (int o0 = 0; o0 < p.M; o0 += kBaThreads) {
     const int o = o0 + tid;
-    const bool f = o < p.M && ba_clamp(p.cam_idx[o], p.n_cam) == c;
+    const bool f = o < p.M && clamp_index(p.cam_idx[o], p.n_cam) == c;
     uint32_t total;
     const uint32_t ex = block_exclusive_scan(f ? 1u : 0u, s_scan, &total);
     if (f && base + ex < end) p.cam_list[base + ex] = o;
@@ -228,16 +157,15 @@ __global__ void __launch_bounds__(kBaThreads) k_ba_fill_cam(BaProblem p) {
 // observation o at state slot `slot`: residual, and with kJac the Jacobian rows
 template <bool kJac>
 SFM_DEV void ba_observe(const BaProblem& p, int o, int slot, double (&r)[2], double (&Jc)[2][6], double (&Jp)[2][3]) {
-  const int c = ba_clamp(p.cam_idx[o], p.n_cam), j = ba_clamp(p.pt_idx[o], p.n_pts);
+  const int c = clamp_index(p.cam_idx[o], p.n_cam), j = clamp_index(p.pt_idx[o], p.n_pts);
   const double* Rt = p.Rt + ((int64_t)slot * p.n_cam + c) * 12;
   const double* Xp = p.Xs + ((int64_t)slot * p.n_pts + j) * 3;
   const double* K = p.K + 9 * c;
   double R[9];
 #pragma unroll
   for (int k = 0; k < 9; ++k) R[k] = Rt[k];
-  const double x = Xp[0], y = Xp[1], z = Xp[2];
-  const double Y[3] = {(R[0] * x + R[1] * y) + R[2] * z, (R[3] * x + R[4] * y) + R[5] * z,
-                       (R[6] * x + R[7] * y) + R[8] * z};
+  double Y[3];
+  rotate3(R, Xp[0], Xp[1], Xp[2], Y);
   const double a0 = Y[0] + Rt[9], a1 = Y[1] + Rt[10], a2 = Y[2] + Rt[11];
   const double q0 = (K[0] * a0 + K[1] * a1) + K[2] * a2;
   const double q1 = (K[3] * a0 + K[4] * a1) + K[5] * a2;
@@ -322,13 +250,13 @@ __global__ void __launch_bounds__(kBaThreads) k_ba_point(BaProblem p) {
   }
   // V* = V + lam diag V = L L^T
   const double a00 = V[0] + lam * V[0], a11 = V[3] + lam * V[3], a22 = V[5] + lam * V[5];
-  bool ok = a00 > 0.0 && ba_finite(a00);
+  bool ok = a00 > 0.0 && finite_f64(a00);
   const double l00 = sqrt(a00), l10 = V[1] / l00, l20 = V[2] / l00;
   const double d1 = a11 - l10 * l10;
-  ok = ok && d1 > 0.0 && ba_finite(d1);
+  ok = ok && d1 > 0.0 && finite_f64(d1);
   const double l11 = sqrt(d1), l21 = (V[4] - l20 * l10) / l11;
   const double d2 = (a22 - l20 * l20) - l21 * l21;
-  ok = ok && d2 > 0.0 && ba_finite(d2);
+  ok = ok && d2 > 0.0 && finite_f64(d2);
   const double l22 = sqrt(d2);
   double Vi[6] = {0, 0, 0, 0, 0, 0};
   if (ok) {  // M = L^-1 (lower), V*^-1 = M^T M
@@ -353,9 +281,9 @@ __global__ void __launch_bounds__(kBaThreads) k_ba_point(BaProblem p) {
   vg[2] = (Vi[2] * g[0] + Vi[4] * g[1]) + Vi[5] * g[2];
   // W_cj at the first observation of (c, j), summed over its duplicates in list order
   for (int e = 0; e < k; ++e) {
-    const int c = ba_clamp(p.cam_idx[p.pt_list[off + e]], p.n_cam);
+    const int c = clamp_index(p.cam_idx[p.pt_list[off + e]], p.n_cam);
     bool first = p.cam_active[c] != 0;
-    for (int f = 0; f < e && first; ++f) first = ba_clamp(p.cam_idx[p.pt_list[off + f]], p.n_cam) != c;
+    for (int f = 0; f < e && first; ++f) first = clamp_index(p.cam_idx[p.pt_list[off + f]], p.n_cam) != c;
     p.lcam[off + e] = first ? c : -1;
     if (!first) continue;
     double W[6][3];
@@ -365,7 +293,7 @@ __global__ void __launch_bounds__(kBaThreads) k_ba_point(BaProblem p) {
       for (int m = 0; m < 3; ++m) W[a][m] = 0.0;
     for (int f = e; f < k; ++f) {
       const int of = p.pt_list[off + f];
-      if (ba_clamp(p.cam_idx[of], p.n_cam) != c) continue;
+      if (clamp_index(p.cam_idx[of], p.n_cam) != c) continue;
       const double* L = p.lin + (int64_t)of * kBaLin;
 #pragma unroll
       for (int a = 0; a < 6; ++a)
@@ -425,7 +353,7 @@ __global__ void __launch_bounds__(64) k_ba_schur(BaProblem p) {
       for (int x = 0; x < 6; ++x) acc[21 + x] += J0[x] * r0 + J1[x] * r1;
     }
 #pragma unroll
-    for (int k = 0; k < 27; ++k) acc[k] = ba_wave_sum(acc[k]);
+    for (int k = 0; k < 27; ++k) acc[k] = wave_sum_f64(acc[k]);
     __syncthreads();
     if (lane == 0) {
       int k = 0;
@@ -450,7 +378,7 @@ __global__ void __launch_bounds__(64) k_ba_schur(BaProblem p) {
       const int ps = p.pos[o];
       if (p.lcam[ps] == a) {  // the first observation of (a, j): the merged block lives here
         my_pos = ps;
-        my_j = ba_clamp(p.pt_idx[o], p.n_pts);
+        my_j = clamp_index(p.pt_idx[o], p.n_pts);
         my_base = p.pt_off[my_j];
         my_k = p.pt_off[my_j + 1] - my_base;
       }
@@ -520,7 +448,7 @@ __global__ void __launch_bounds__(kBaSolveThreads) k_ba_solve(BaProblem p) {
     __syncthreads();  // the trailing update of column k - 1 is done
     if (tid == 0) {
       const double d = A[(int64_t)k * n + k];
-      if (d > 0.0 && ba_finite(d)) {
+      if (d > 0.0 && finite_f64(d)) {
         A[(int64_t)k * n + k] = s_col[k] = sqrt(d);
       } else {
         s_fail = 1;
@@ -607,12 +535,8 @@ __global__ void __launch_bounds__(kBaThreads) k_ba_update(BaProblem p) {
     for (int k = 0; k < 6; ++k) d[k] = act ? p.delta[6 * c + k] : 0.0;
     if (act) {
       double E[9];
-      ba_rodrigues(d[0], d[1], d[2], E);
-#pragma unroll
-      for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-          Rn[3 * r + k] = (E[3 * r] * Rt[k] + E[3 * r + 1] * Rt[3 + k]) + E[3 * r + 2] * Rt[6 + k];
+      rodrigues(d[0], d[1], d[2], E);
+      compose3(E, Rt, Rn);
 #pragma unroll
       for (int k = 0; k < 3; ++k) Rn[9 + k] = Rt[9 + k] + d[3 + k];
     } else {
@@ -635,7 +559,7 @@ __global__ void __launch_bounds__(kBaThreads) k_ba_decide(BaProblem p, int first
   const int tid = threadIdx.x;
   double acc = 0.0;
   for (int i = tid; i < p.M; i += kBaThreads) acc += p.e2[i];
-  const double cost_new = ba_block_sum(acc, s_red);
+  const double cost_new = block_sum256_tree(acc, s_red);
   double d2 = 0.0, p2 = 0.0;
   if (!first) {
     const int64_t rows = (int64_t)p.n_pts + p.n_cam;
@@ -644,13 +568,13 @@ __global__ void __launch_bounds__(kBaThreads) k_ba_decide(BaProblem p, int first
       ad += p.nrm[2 * i];
       ap += p.nrm[2 * i + 1];
     }
-    d2 = ba_block_sum(ad, s_red);
-    p2 = ba_block_sum(ap, s_red);
+    d2 = block_sum256_tree(ad, s_red);
+    p2 = block_sum256_tree(ap, s_red);
   }
   if (tid != 0) return;
   if (first) {
     s->cost0 = s->cost = cost_new;
-    if (!ba_finite(cost_new)) {
+    if (!finite_f64(cost_new)) {
       s->status = kRefineNonFinite;
       s->done = 1;
     }
@@ -659,7 +583,7 @@ __global__ void __launch_bounds__(kBaThreads) k_ba_decide(BaProblem p, int first
   s->iters += 1;
   if (s->fail) s->rejected += 1;
   const double cost = s->cost;
-  if (!s->fail && ba_finite(cost_new) && cost_new < cost) {
+  if (!s->fail && finite_f64(cost_new) && cost_new < cost) {
     const double rel = (cost - cost_new) / cost;
     s->accepted += 1;
     s->cost = cost_new;
@@ -704,7 +628,7 @@ __global__ void __launch_bounds__(kBaThreads) k_ba_finish(BaProblem p) {
       double R[9], r[3];
 #pragma unroll
       for (int k = 0; k < 9; ++k) R[k] = Rt[k];
-      ba_rodrigues_inv(R, r);
+      rodrigues_inv(R, r);
 #pragma unroll
       for (int k = 0; k < 3; ++k) o[k] = r[k], o[3 + k] = Rt[9 + k];
     } else {  // a row that never moved: its input bits

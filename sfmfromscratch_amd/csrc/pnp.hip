@@ -31,6 +31,7 @@
 
 #include <algorithm>
 
+#include "f64_dev.h"
 #include "kernels.h"
 #include "linalg3.h"
 
@@ -38,8 +39,6 @@ namespace sfm {
 
 constexpr int kPnpWaves = 8;     // samples (waves) per workgroup of k_pnp_count
 constexpr int kPnpThreads = 256; // k_pnp_select, k_pnp_refine, k_pnp_dlt_all
-
-SFM_DEV bool pnp_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }  // false for NaN
 
 // K^-1 (u, v, 1) for upper-triangular K, by back substitution
 SFM_DEV void normalised_pixel(const double* __restrict__ K, double u, double v, double& un, double& vn) {
@@ -89,14 +88,14 @@ SFM_DEV void pose_from_p(const double (&p)[12], double s, const double (&c)[3], 
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       Rt[3 * r + k] = (M[r][0] * B[0][k] + M[r][1] * B[1][k]) + M[r][2] * B[2][k];
-      ok = ok && pnp_finite(Rt[3 * r + k]);
+      ok = ok && finite_f64(Rt[3 * r + k]);
     }
   }
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
     const double Rc = (Rt[3 * r] * c[0] + Rt[3 * r + 1] * c[1]) + Rt[3 * r + 2] * c[2];
     Rt[9 + r] = (p4[r] / sigma - s * Rc) / s;
-    ok = ok && pnp_finite(Rt[9 + r]);
+    ok = ok && finite_f64(Rt[9 + r]);
   }
   if (!ok) {
 #pragma unroll
@@ -118,8 +117,7 @@ __global__ void __launch_bounds__(64) k_pnp_hyp(const double* __restrict__ X, co
   double Xs[6][3], un[6], vn[6];
 #pragma unroll
   for (int i = 0; i < 6; ++i) {
-    int j = idx[(int64_t)it * stride + i];
-    j = j < 0 ? 0 : (j >= n ? n - 1 : j);
+    const int j = clamp_index(idx[(int64_t)it * stride + i], n);
 #pragma unroll
     for (int k = 0; k < 3; ++k) Xs[i][k] = X[3 * (int64_t)j + k];
     normalised_pixel(K, x[2 * (int64_t)j], x[2 * (int64_t)j + 1], un[i], vn[i]);
@@ -212,9 +210,9 @@ __global__ void __launch_bounds__(64) k_pnp_hyp(const double* __restrict__ X, co
 // depth > 0 and |pi(K (R X + t)) - x| < thr; a NaN compares false
 SFM_DEV bool pnp_inlier(const double (&Kc)[6], const double (&R)[9], const double (&t)[3], double X0, double X1,
                         double X2, double u, double v, double thr) {
-  const double a0 = ((R[0] * X0 + R[1] * X1) + R[2] * X2) + t[0];
-  const double a1 = ((R[3] * X0 + R[4] * X1) + R[5] * X2) + t[1];
-  const double a2 = ((R[6] * X0 + R[7] * X1) + R[8] * X2) + t[2];
+  double Y[3];
+  rotate3(R, X0, X1, X2, Y);
+  const double a0 = Y[0] + t[0], a1 = Y[1] + t[1], a2 = Y[2] + t[2];
   const double q0 = (Kc[0] * a0 + Kc[1] * a1) + Kc[2] * a2;
   const double q1 = Kc[3] * a1 + Kc[4] * a2;
   const double q2 = Kc[5] * a2;
@@ -244,7 +242,7 @@ __global__ void __launch_bounds__(64 * kPnpWaves) k_pnp_count(const double* __re
   for (int k = 0; k < 9; ++k) R[k] = H[k];
 #pragma unroll
   for (int k = 0; k < 3; ++k) t[k] = H[9 + k];
-  const bool live = have && pnp_finite(R[0]);  // (a NaN hypothesis is NaN throughout)
+  const bool live = have && finite_f64(R[0]);  // (a NaN hypothesis is NaN throughout)
   uint32_t c = 0;
   for (int i0 = 0; i0 < n; i0 += kRansacChunk) {
     const int m = min(kRansacChunk, n - i0);
@@ -348,10 +346,9 @@ constexpr int kPnpSums = 28;  // J^T J upper triangle (21, row-major), J^T r (6)
 // Y = R X and g_a = d r_a / d X_c
 SFM_DEV void pnp_accumulate(const double (&Kc)[6], const double (&R)[9], const double (&t)[3], double X0, double X1,
                             double X2, double u, double v, double (&acc)[kPnpSums]) {
-  const double Y0 = (R[0] * X0 + R[1] * X1) + R[2] * X2;
-  const double Y1 = (R[3] * X0 + R[4] * X1) + R[5] * X2;
-  const double Y2 = (R[6] * X0 + R[7] * X1) + R[8] * X2;
-  const double a0 = Y0 + t[0], a1 = Y1 + t[1], a2 = Y2 + t[2];
+  double Y[3];
+  rotate3(R, X0, X1, X2, Y);
+  const double a0 = Y[0] + t[0], a1 = Y[1] + t[1], a2 = Y[2] + t[2];
   const double q0 = (Kc[0] * a0 + Kc[1] * a1) + Kc[2] * a2;
   const double q1 = Kc[3] * a1 + Kc[4] * a2;
   const double q2 = Kc[5] * a2;
@@ -359,8 +356,10 @@ SFM_DEV void pnp_accumulate(const double (&Kc)[6], const double (&R)[9], const d
   const double r0 = pu - u, r1 = pv - v;
   const double g0[3] = {Kc[0] / q2, Kc[1] / q2, (Kc[2] - pu * Kc[5]) / q2};
   const double g1[3] = {0.0, Kc[3] / q2, (Kc[4] - pv * Kc[5]) / q2};
-  const double J0[6] = {Y1 * g0[2] - Y2 * g0[1], Y2 * g0[0] - Y0 * g0[2], Y0 * g0[1] - Y1 * g0[0], g0[0], g0[1], g0[2]};
-  const double J1[6] = {Y1 * g1[2] - Y2 * g1[1], Y2 * g1[0] - Y0 * g1[2], Y0 * g1[1] - Y1 * g1[0], g1[0], g1[1], g1[2]};
+  const double J0[6] = {Y[1] * g0[2] - Y[2] * g0[1], Y[2] * g0[0] - Y[0] * g0[2], Y[0] * g0[1] - Y[1] * g0[0],
+                        g0[0], g0[1], g0[2]};
+  const double J1[6] = {Y[1] * g1[2] - Y[2] * g1[1], Y[2] * g1[0] - Y[0] * g1[2], Y[0] * g1[1] - Y[1] * g1[0],
+                        g1[0], g1[1], g1[2]};
   int k = 0;
 #pragma unroll
   for (int a = 0; a < 6; ++a)
@@ -369,12 +368,6 @@ SFM_DEV void pnp_accumulate(const double (&Kc)[6], const double (&R)[9], const d
 #pragma unroll
   for (int a = 0; a < 6; ++a) acc[21 + a] = fma(J1[a], r1, fma(J0[a], r0, acc[21 + a]));
   acc[27] = fma(r1, r1, fma(r0, r0, acc[27]));
-}
-
-SFM_DEV double wave_sum_f64(double v) {  // every lane gets the same bits (a + b == b + a at every level)
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-  return v;
 }
 
 // sums over the m points (inl: their indices, or nullptr for 0..m-1) at (R, t); every thread gets them
@@ -386,8 +379,7 @@ SFM_DEV void pnp_evaluate(const double* __restrict__ X, const double* __restrict
 #pragma unroll
   for (int k = 0; k < kPnpSums; ++k) acc[k] = 0.0;
   for (int i = tid; i < m; i += kPnpThreads) {
-    int j = inl ? inl[i] : i;
-    j = j < 0 ? 0 : (j >= n ? n - 1 : j);
+    const int j = clamp_index(inl ? inl[i] : i, n);
     pnp_accumulate(Kc, R, t, X[3 * (int64_t)j], X[3 * (int64_t)j + 1], X[3 * (int64_t)j + 2], x[2 * (int64_t)j],
                    x[2 * (int64_t)j + 1], acc);
   }
@@ -441,30 +433,6 @@ SFM_DEV void pnp_solve6(const double (&s)[kPnpSums], double lam, double (&d)[6])
   }
 }
 
-// exp([w]x) R: the closed form of k_total_reproj (identity below DBL_EPSILON)
-SFM_DEV void pnp_rotate(const double (&d)[6], const double (&R)[9], double (&Rn)[9]) {
-  const double r0 = d[0], r1 = d[1], r2 = d[2];
-  const double th = sqrt((r0 * r0 + r1 * r1) + r2 * r2);
-  double E[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
-  if (!(th < 2.220446049250313e-16)) {
-    const double cs = cos(th), sn = sin(th), c1 = 1.0 - cs;
-    const double kx = r0 / th, ky = r1 / th, kz = r2 / th;
-    E[0] = cs + c1 * kx * kx;
-    E[1] = c1 * kx * ky - sn * kz;
-    E[2] = c1 * kx * kz + sn * ky;
-    E[3] = c1 * kx * ky + sn * kz;
-    E[4] = cs + c1 * ky * ky;
-    E[5] = c1 * ky * kz - sn * kx;
-    E[6] = c1 * kx * kz - sn * ky;
-    E[7] = c1 * ky * kz + sn * kx;
-    E[8] = cs + c1 * kz * kz;
-  }
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int k = 0; k < 3; ++k) Rn[3 * r + k] = (E[3 * r] * R[k] + E[3 * r + 1] * R[3 + k]) + E[3 * r + 2] * R[6 + k];
-}
-
 // Rt_in: the start pose (R, t).  count_p (with inl): the number of inliers on the device, <= 0
 // for "no pose"; without inl the n points themselves.  out_status: found, LM status, accepted
 // steps, iterations run; out_cost: the cost at the start and at the returned pose.
@@ -486,7 +454,7 @@ __global__ void __launch_bounds__(kPnpThreads) k_pnp_refine(const double* __rest
   for (int k = 0; k < 9; ++k) R[k] = Rt_in[k];
 #pragma unroll
   for (int k = 0; k < 3; ++k) t[k] = Rt_in[9 + k];
-  if (m <= 0 || !pnp_finite(R[0])) {  // no pose (uniform over the workgroup)
+  if (m <= 0 || !finite_f64(R[0])) {  // no pose (uniform over the workgroup)
     if (tid < 9) out_R[tid] = __builtin_nan("");
     if (tid < 3) out_t[tid] = __builtin_nan("");
     if (tid < 2) out_cost[tid] = __builtin_nan("");
@@ -499,15 +467,16 @@ __global__ void __launch_bounds__(kPnpThreads) k_pnp_refine(const double* __rest
   pnp_evaluate(X, x, inl, m, n, Kc, R, t, s_red, cur);
   const double cost0 = cur[27];
   int accepted = 0, ran = 0, status = kRefineMaxIter;
-  if (!pnp_finite(cost0)) {
+  if (!finite_f64(cost0)) {
     status = kRefineNonFinite;
   } else {
     double lam = 1e-3;
     for (int it = 0; it < max_iter; ++it) {
       ++ran;
-      double d[6], Rn[9], tn[3], tr[kPnpSums];
+      double d[6], E[9], Rn[9], tn[3], tr[kPnpSums];
       pnp_solve6(cur, lam, d);
-      pnp_rotate(d, R, Rn);
+      rodrigues(d[0], d[1], d[2], E);  // Rn = exp([d omega]x) R
+      compose3(E, R, Rn);
 #pragma unroll
       for (int k = 0; k < 3; ++k) tn[k] = t[k] + d[3 + k];
       pnp_evaluate(X, x, inl, m, n, Kc, Rn, tn, s_red, tr);
@@ -556,7 +525,10 @@ __global__ void __launch_bounds__(kPnpThreads) k_pnp_refine(const double* __rest
 
 constexpr int kPnpDltSums = 40;  // 10 each of sum W, sum u W, sum v W, sum (u^2 + v^2) W
 
-SFM_DEV double block_sum_f64(double v, double* s4) {  // wave butterflies, then the four waves in order
+// the sum over 256 threads as pnp_evaluate takes it: wave butterflies, then the four waves in
+// order; every thread gets the sum.  (f64_dev.h's block_sum256_tree sums in another order: the
+// two do not agree in the last bit.)
+SFM_DEV double block_sum256_waves(double v, double* s4) {
   const int tid = threadIdx.x;
   const double w = wave_sum_f64(v);
   __syncthreads();
@@ -583,14 +555,14 @@ __global__ void __launch_bounds__(kPnpThreads) k_pnp_dlt_all(const double* __res
   for (int k = 0; k < 3; ++k) {
     double a = 0.0;
     for (int i = tid; i < n; i += kPnpThreads) a += X[3 * (int64_t)i + k];
-    c[k] = block_sum_f64(a, s4) / (double)n;
+    c[k] = block_sum256_waves(a, s4) / (double)n;
   }
   double sd = 0.0;
   for (int i = tid; i < n; i += kPnpThreads) {
     const double dx = X[3 * (int64_t)i] - c[0], dy = X[3 * (int64_t)i + 1] - c[1], dz = X[3 * (int64_t)i + 2] - c[2];
     sd += sqrt((dx * dx + dy * dy) + dz * dz);
   }
-  const double s = sqrt(3.0) / (block_sum_f64(sd, s4) / (double)n);
+  const double s = sqrt(3.0) / (block_sum256_waves(sd, s4) / (double)n);
   double acc[kPnpDltSums];
 #pragma unroll
   for (int k = 0; k < kPnpDltSums; ++k) acc[k] = 0.0;

@@ -29,6 +29,7 @@
 
 #include <algorithm>
 
+#include "f64_dev.h"  // block_sum256_tree
 #include "kernels.h"
 #include "linalg3.h"  // jacobi_eig3, det3
 #include "linalg4.h"  // null_vector_4x4
@@ -271,18 +272,6 @@ void launch_pose_gather(const int32_t* out_iter, const double* cand, const int32
 
 // ---------------- triangulation over N points ----------------
 
-SFM_DEV double block_sum256(double v, double* s) {  // every thread gets the sum (fixed tree)
-  const int tid = threadIdx.x;
-  __syncthreads();
-  s[tid] = v;
-  __syncthreads();
-  for (int off = 128; off >= 1; off >>= 1) {
-    if (tid < off) s[tid] += s[tid + off];
-    __syncthreads();
-  }
-  return s[0];
-}
-
 // CameraPose.normalize_points (SFM.py:163-178) of both point sets and T1 P1, T2 P2
 // (:297-298): one workgroup; out = the two normalised matrices (24) then s, cu, cv of each set
 __global__ void __launch_bounds__(256) k_hartley(const double* __restrict__ x1, const double* __restrict__ x2,
@@ -298,14 +287,14 @@ __global__ void __launch_bounds__(256) k_hartley(const double* __restrict__ x1, 
       sx += x[2 * i];
       sy += x[2 * i + 1];
     }
-    const double cu = block_sum256(sx, s_red) / (double)N;
-    const double cv = block_sum256(sy, s_red) / (double)N;
+    const double cu = block_sum256_tree(sx, s_red) / (double)N;
+    const double cv = block_sum256_tree(sy, s_red) / (double)N;
     double sd = 0.0;
     for (int64_t i = tid; i < N; i += 256) {
       const double dx = x[2 * i] - cu, dy = x[2 * i + 1] - cv;
       sd += sqrt(dx * dx + dy * dy);
     }
-    const double sc = sqrt(2.0) / (block_sum256(sd, s_red) / (double)N);
+    const double sc = sqrt(2.0) / (block_sum256_tree(sd, s_red) / (double)N);
     if (tid < 4) {
       out[12 * set + tid] = sc * Pm[tid] + (-sc * cu) * Pm[8 + tid];
       out[12 * set + 4 + tid] = sc * Pm[4 + tid] + (-sc * cv) * Pm[8 + tid];

@@ -12,7 +12,7 @@
 //   whose initial cost is not finite is returned unchanged (2).  A failed factorisation gives
 //   a non-finite d and so a rejected step.
 // * k_reproj_error / k_reproj_mean: Util.print_reprojection_error (Util.py:65-82): the two
-//   norms per point, and their mean by one workgroup's fixed-order tree (no atomics).
+//   norms per point, and their mean by one workgroup's block_sum256_tree (no atomics).
 // * k_link_points / k_link_compact: the 2D -> 3D association loop (Runner.py:241-250) on
 //   integer pixels: per query the first target of the smallest squared distance (int64,
 //   exact), kept iff sqrt((double)d2) < threshold; kept pairs compacted in query order.
@@ -23,6 +23,7 @@
 
 #include <algorithm>
 
+#include "f64_dev.h"
 #include "kernels.h"
 
 namespace sfm {
@@ -56,8 +57,6 @@ SFM_DEV void evaluate_point(const double (&P1)[12], const double (&P2)[12], cons
   e.cost = fma(e.r[3], e.r[3], fma(e.r[2], e.r[2], fma(e.r[1], e.r[1], e.r[0] * e.r[0])));
 }
 
-SFM_DEV bool finite_f64(double v) { return fabs(v) <= 1.7976931348623157e308; }  // false for NaN
-
 __global__ void __launch_bounds__(128) k_refine_points(const double* X0, const double* __restrict__ x1,
                                                        const double* __restrict__ x2, int64_t N,
                                                        const double* __restrict__ Pm, int S,
@@ -65,8 +64,7 @@ __global__ void __launch_bounds__(128) k_refine_points(const double* X0, const d
                                                        double* __restrict__ cost, int32_t* __restrict__ iters) {
   const int64_t i = (int64_t)blockIdx.x * 128 + threadIdx.x;
   if (i >= N) return;
-  int s = seg ? seg[i] : 0;
-  s = s < 0 ? 0 : (s >= S ? S - 1 : s);
+  const int s = clamp_index(seg ? seg[i] : 0, S);
   double P1[12], P2[12];
 #pragma unroll
   for (int k = 0; k < 12; ++k) {
@@ -168,21 +166,16 @@ __global__ void __launch_bounds__(128) k_reproj_error(const double* __restrict__
   err[2 * i + 1] = sqrt(e.r[2] * e.r[2] + e.r[3] * e.r[3]);
 }
 
-// mean over points of (e1 + e2) / 2 (Util.py:81): strided partial sums in index order, then a
-// fixed tree over the 256 threads: the same bits every run.  N == 0 gives NaN, as np.mean([]).
+// mean over points of (e1 + e2) / 2 (Util.py:81): strided partial sums in index order, then
+// block_sum256_tree: the same bits every run.  N == 0 gives NaN, as np.mean([]).
 __global__ void __launch_bounds__(256) k_reproj_mean(const double* __restrict__ err, int64_t N,
                                                      double* __restrict__ mean) {
   __shared__ double s_red[256];
   const int tid = threadIdx.x;
   double acc = 0.0;
   for (int64_t i = tid; i < N; i += 256) acc += (err[2 * i] + err[2 * i + 1]) / 2.0;
-  s_red[tid] = acc;
-  __syncthreads();
-  for (int off = 128; off >= 1; off >>= 1) {
-    if (tid < off) s_red[tid] += s_red[tid + off];
-    __syncthreads();
-  }
-  if (tid == 0) *mean = N > 0 ? s_red[0] / (double)N : __builtin_nan("");
+  const double sum = block_sum256_tree(acc, s_red);
+  if (tid == 0) *mean = N > 0 ? sum / (double)N : __builtin_nan("");
 }
 
 void launch_reproj_error(const double* X, const double* x1, const double* x2, int64_t N, const double* P1,

@@ -27,7 +27,7 @@
 //   and flags are written, the new coordinates appended and the device-resident count
 //   updated.  The serial part is the walk over contested points only.
 // * k_total_reproj / k_total_mean: per observation |pi(K (R X + t)) - obs| with R from the
-//   Rodrigues vector in closed form, and the mean by one workgroup's fixed-order tree.
+//   Rodrigues vector (linalg3.h rodrigues), and the mean by one workgroup's block_sum256_tree.
 // Float64 throughout; -ffp-contract=off (no fused multiply-add anywhere in this file: the
 // distance is numpy's (dx*dx + dy*dy) + dz*dz).
 #include <math.h>
@@ -35,7 +35,9 @@
 
 #include <algorithm>
 
+#include "f64_dev.h"
 #include "kernels.h"
+#include "linalg3.h"
 
 namespace sfm {
 
@@ -289,30 +291,12 @@ __global__ void __launch_bounds__(128) k_total_reproj(const int32_t* __restrict_
                                                       int n_pts, double* __restrict__ err) {
   const int64_t o = (int64_t)blockIdx.x * 128 + threadIdx.x;
   if (o >= M) return;
-  int c = cam_idx[o], p = pt_idx[o];
-  c = c < 0 ? 0 : (c >= n_cam ? n_cam - 1 : c);  // (indices are the caller's contract)
-  p = p < 0 ? 0 : (p >= n_pts ? n_pts - 1 : p);
+  const int c = clamp_index(cam_idx[o], n_cam), p = clamp_index(pt_idx[o], n_pts);
   const double* cp = cams + 6 * (int64_t)c;
-  const double r0 = cp[0], r1 = cp[1], r2 = cp[2];
-  const double th = sqrt((r0 * r0 + r1 * r1) + r2 * r2);
-  double R[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};
-  if (!(th < 2.220446049250313e-16)) {  // cv2.Rodrigues: identity below DBL_EPSILON
-    const double cs = cos(th), sn = sin(th), c1 = 1.0 - cs;
-    const double kx = r0 / th, ky = r1 / th, kz = r2 / th;
-    R[0] = cs + c1 * kx * kx;
-    R[1] = c1 * kx * ky - sn * kz;
-    R[2] = c1 * kx * kz + sn * ky;
-    R[3] = c1 * kx * ky + sn * kz;
-    R[4] = cs + c1 * ky * ky;
-    R[5] = c1 * ky * kz - sn * kx;
-    R[6] = c1 * kx * kz - sn * ky;
-    R[7] = c1 * ky * kz + sn * kx;
-    R[8] = cs + c1 * kz * kz;
-  }
-  const double x = X[3 * (int64_t)p], y = X[3 * (int64_t)p + 1], z = X[3 * (int64_t)p + 2];
-  const double a0 = (R[0] * x + R[1] * y + R[2] * z) + cp[3];
-  const double a1 = (R[3] * x + R[4] * y + R[5] * z) + cp[4];
-  const double a2 = (R[6] * x + R[7] * y + R[8] * z) + cp[5];
+  double R[9], Y[3];
+  rodrigues(cp[0], cp[1], cp[2], R);
+  rotate3(R, X[3 * (int64_t)p], X[3 * (int64_t)p + 1], X[3 * (int64_t)p + 2], Y);
+  const double a0 = Y[0] + cp[3], a1 = Y[1] + cp[4], a2 = Y[2] + cp[5];
   const double* K = Kg + 9 * (int64_t)c;
   const double q0 = K[0] * a0 + K[1] * a1 + K[2] * a2;
   const double q1 = K[3] * a0 + K[4] * a1 + K[5] * a2;
@@ -321,21 +305,16 @@ __global__ void __launch_bounds__(128) k_total_reproj(const int32_t* __restrict_
   err[o] = sqrt(ex * ex + ey * ey);
 }
 
-// mean over the M observations: strided partial sums in index order, then a fixed tree over
-// the 256 threads (k_reproj_mean's shape): the same bits every run.  M == 0 gives NaN.
+// mean over the M observations: strided partial sums in index order, then block_sum256_tree:
+// the same bits every run.  M == 0 gives NaN.
 __global__ void __launch_bounds__(256) k_total_mean(const double* __restrict__ err, int64_t M,
                                                     double* __restrict__ mean) {
   __shared__ double s_red[256];
   const int tid = threadIdx.x;
   double acc = 0.0;
   for (int64_t i = tid; i < M; i += 256) acc += err[i];
-  s_red[tid] = acc;
-  __syncthreads();
-  for (int off = 128; off >= 1; off >>= 1) {
-    if (tid < off) s_red[tid] += s_red[tid + off];
-    __syncthreads();
-  }
-  if (tid == 0) *mean = M > 0 ? s_red[0] / (double)M : __builtin_nan("");
+  const double sum = block_sum256_tree(acc, s_red);
+  if (tid == 0) *mean = M > 0 ? sum / (double)M : __builtin_nan("");
 }
 
 void launch_total_reproj(const int32_t* cam_idx, const int32_t* pt_idx, const double* obs, int64_t M,

