@@ -632,6 +632,28 @@ int32_t sfm_debug_harris(int32_t device, const float* gauss, int32_t gs, double 
                          int32_t ksize, const float* img, int32_t H, int32_t W, float* R_out,
                          float* median_out, int64_t* ncand_out);
 
+/* The float64 helpers the geometry kernels share (csrc/linalg3.h, linalg4.h, f64_dev.h), each
+ * run by itself on n rows of host data (synchronises; only reads `in`), so that a helper can be
+ * tested where no stage reaches.  Doubles per row, in -> out:
+ *   RODRIGUES      r[3] -> R[9]                       RODRIGUES_INV  R[9] -> r[3]
+ *   EIG3           s00 s01 s02 s11 s12 s22 -> the 3 diagonal entries after, then V[9] row-major
+ *   NULL4          A[16] row-major -> v[4]            COMPOSE        E[9], R[9] -> E R [9]
+ *   ROTATE         R[9], x, y, z -> Y[3]              (one thread per row up to here)
+ *   WAVE_SUM       64 values -> each lane's own result of wave_sum_f64 (one wave per row)
+ *   BLOCK_SUM      2 x 256 values -> what each of the 256 threads got from block_sum256_tree of
+ *                  the first 256 and then, on the same LDS array, of the second (2 x 256)
+ * SFM_EINVAL: a null pointer, n < 0 or n > 2^20, an unknown op; n == 0 launches nothing. */
+#define SFM_GEOM_RODRIGUES 0
+#define SFM_GEOM_RODRIGUES_INV 1
+#define SFM_GEOM_EIG3 2
+#define SFM_GEOM_NULL4 3
+#define SFM_GEOM_COMPOSE 4
+#define SFM_GEOM_ROTATE 5
+#define SFM_GEOM_WAVE_SUM 6
+#define SFM_GEOM_BLOCK_SUM 7
+#define SFM_GEOM_OPS 8
+int32_t sfm_debug_geom(int32_t device, int32_t op, const double* in, int64_t n, double* out);
+
 /* Certified-mode NMS candidates (NaiveSIFT.py:77-95 with keys >= tnms[b]) of B planes:
  * unordered u64 keys ~fkey(R) << 32 | raster index in keys_out[b*H*W ...], counts_out[b] of
  * them.  tile = 1 forces the tiled kernel where the streaming one runs by default. */

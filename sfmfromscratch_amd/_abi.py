@@ -54,6 +54,16 @@ MATCH_DEBUG_SIGNATURES = {
     # ctx, pair, rows, cand_n, cand_thr, cand
     "sfm_debug_match_windows": (ctypes.c_int32, [_vp, ctypes.c_int32, ctypes.c_int64, _vp, _vp, _vp]),
 }
+# include/sfmfeat.h's probe of the geometry kernels' shared float64 helpers (host pointers as void*;
+# tests/test_abi_cpu.py holds it against the header's prototype): device, op, in, n, out
+GEOM_DEBUG_SIGNATURES = {
+    "sfm_debug_geom": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, _vp, ctypes.c_int64, _vp]),
+}
+(SFM_GEOM_RODRIGUES, SFM_GEOM_RODRIGUES_INV, SFM_GEOM_EIG3, SFM_GEOM_NULL4, SFM_GEOM_COMPOSE, SFM_GEOM_ROTATE,
+ SFM_GEOM_WAVE_SUM, SFM_GEOM_BLOCK_SUM) = range(8)
+GEOM_ROW_IN = (3, 9, 6, 16, 18, 12, 64, 512)    # doubles per row, by op
+GEOM_ROW_OUT = (9, 3, 12, 4, 9, 3, 64, 512)
+SFM_GEOM_MAX_ROWS = 1 << 20
 MATCH_CAND_CAP = 256   # list words per query row (two half-lists of 128)
 MATCH_PREP_ROWS = 16   # rows per block of the operands' (norm2, rnorm) maxima
 

@@ -107,6 +107,7 @@ SIGNATURES = {
     "sfm_debug_match_stamps": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int64]),
     "sfm_debug_select_stats": (ctypes.c_int32, [_vp, _i32p, _i32p]),
     **_abi.MATCH_DEBUG_SIGNATURES,  # sfm_debug_match_operands, sfm_debug_match_windows
+    **_abi.GEOM_DEBUG_SIGNATURES,  # sfm_debug_geom
     "sfm_copy_wg": (ctypes.c_int32, [_vp, _vp, ctypes.c_int64, ctypes.c_int32, _vp]),
     "sfm_dist_unique_id": (ctypes.c_int32, [_u8p]),
     "sfm_dist_create": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _u8p, ctypes.POINTER(_vp)]),
@@ -570,6 +571,25 @@ def debug_nms(R: np.ndarray, tnms, ksize: int = 3, tile: bool = False, device: i
     check(load_library().sfm_debug_nms(device, R.ctypes.data_as(_fp), B, H, W, ksize, t.ctypes.data,
                                        int(tile), keys.ctypes.data, cnt.ctypes.data_as(_i64p)))
     return [np.sort(keys[b * H * W: b * H * W + cnt[b]]) for b in range(B)]
+
+
+def debug_geom(op: int, rows: np.ndarray, device: int = 0) -> np.ndarray:
+    """sfm_debug_geom: one shared float64 helper of the geometry kernels on every row of `rows`
+    (C-contiguous float64 [n, _abi.GEOM_ROW_IN[op]]) -> float64 [n, _abi.GEOM_ROW_OUT[op]]."""
+    op = int(op)
+    if not 0 <= op < len(_abi.GEOM_ROW_IN):
+        raise ValueError(f"debug_geom: unknown op {op}")
+    if not isinstance(rows, np.ndarray) or rows.dtype != np.float64 or not rows.flags.c_contiguous:
+        raise ValueError("debug_geom: rows must be a C-contiguous float64 array")
+    if rows.ndim != 2 or rows.shape[1] != _abi.GEOM_ROW_IN[op]:
+        raise ValueError(f"debug_geom: op {op} takes rows of {_abi.GEOM_ROW_IN[op]} values, got shape {rows.shape}")
+    n = rows.shape[0]
+    if n > _abi.SFM_GEOM_MAX_ROWS:
+        raise ValueError(f"debug_geom: at most {_abi.SFM_GEOM_MAX_ROWS} rows")
+    out = np.empty((n, _abi.GEOM_ROW_OUT[op]), np.float64)
+    if n:
+        check(load_library().sfm_debug_geom(device, op, rows.ctypes.data, n, out.ctypes.data))
+    return out
 
 
 class Gate:

@@ -218,8 +218,10 @@ def cost_of(sc, cams, X):
 # ---------------- planted scenes ----------------
 
 def scene(seed, n_cam, n_pts, views, fixed=(), noise=0.5, pert=0.02, dup=0, idle_cam=False, idle_pt=False,
-          exact_cam=None, M=None, heavy_cam=None):
+          exact_cam=None, M=None, heavy_cam=None, arc=0.5, tilt=1.0):
     """A ring of cameras looking at a point cloud.  views(j, rng) -> the cameras that see point j.
+    arc: the cameras turn about y by angles spread over [-arc, arc] (pi: a whole orbit); tilt scales
+    the x and z components of their rotation vectors (0: pure y rotations).
     noise: pixels; pert: the start's offset from the planted model.  dup: that many observations
     repeated (a second measurement of the same (c, j)); idle_cam / idle_pt append a camera / a
     point nothing observes; exact_cam: a camera whose observations are the start's own
@@ -230,8 +232,8 @@ def scene(seed, n_cam, n_pts, views, fixed=(), noise=0.5, pert=0.02, dup=0, idle
     cams_t = np.zeros((n_cam, 6))
     K = np.zeros((n_cam, 3, 3))
     for c in range(n_cam):
-        ang = 0.5 * (c - (n_cam - 1) / 2.0) / max(n_cam - 1, 1) * 2.0
-        w = np.array([0.1 * np.sin(3.0 * c), ang, 0.05 * np.cos(2.0 * c)])
+        ang = arc * (c - (n_cam - 1) / 2.0) / max(n_cam - 1, 1) * 2.0
+        w = np.array([tilt * 0.1 * np.sin(3.0 * c), ang, tilt * 0.05 * np.cos(2.0 * c)])
         Rm = rodrigues_to_matrix(w)
         centre = np.array([4.0 * np.sin(ang), 0.3 * np.cos(c), -4.0 * np.cos(ang)])
         cams_t[c, :3], cams_t[c, 3:] = w, -Rm @ centre
@@ -325,6 +327,44 @@ def cases():
         c[f"camlist_{k}"] = scene(30 + k % 10, 2, 260, _all(2), fixed=(0,), heavy_cam=(1, k))
     c["obs_2000"] = scene(40, 4, 500, _all(4), fixed=(0, 1))                        # M = 2,000
     return c
+
+
+RING_SEED = 80
+
+
+def _ring(n_cam):
+    """each point seen by cameras j, j + 1, j + 2 and j + 4 (mod n_cam)."""
+    return lambda j, rng: sorted({j % n_cam, (j + 1) % n_cam, (j + 2) % n_cam, (j + 4) % n_cam})
+
+
+NONPRINCIPAL_CAMS = {1: -1, 7: +1}   # ring9_nonprincipal: camera -> whole turns added to its start angle
+
+
+def ring_cases():
+    """name -> scene: cameras that orbit the cloud, so that their rotations pass pi / 2 and come
+    close to pi (cases() stays within 0.52 rad).  Apart from cases(): the fixture holds none of
+    them; the restatement solves them at test time, as for many_cameras."""
+    c = {}
+    c["ring9"] = scene(RING_SEED, 9, 48, _ring(9), fixed=(4, 5), arc=np.pi)
+    c["ring9_flat"] = scene(RING_SEED, 9, 48, _ring(9), fixed=(4, 5), arc=np.pi, tilt=0.0)   # pure y rotations
+    c["ring8"] = scene(RING_SEED, 8, 48, _ring(8), fixed=(3, 4), arc=7.0 * np.pi / 8.0)
+    c["ring5_quarter"] = scene(RING_SEED, 5, 48, _ring(5), fixed=(2, 3), arc=np.pi / 2.0, tilt=0.0)
+    sc = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in c["ring9"].items()}
+    for cam, turns in NONPRINCIPAL_CAMS.items():     # the same rotations, one turn below and one above
+        w = sc["cams"][cam, :3]
+        th = np.sqrt(w @ w)
+        sc["cams"][cam, :3] = w / th * (th + turns * 2.0 * np.pi)
+    c["ring9_nonprincipal"] = sc
+    return c
+
+
+def rotation_angles(cams):
+    """(c [n], theta [n]) of the cameras' rotations as rodrigues_inv sees them: c = (trace - 1) / 2,
+    whose sign chooses the branch, and theta = atan2(s, c) in [0, pi]."""
+    R = np.array([rodrigues_to_matrix(w) for w in np.asarray(cams)[:, :3]])
+    c = (np.trace(R, axis1=1, axis2=2) - 1.0) / 2.0
+    v = np.stack([R[:, 2, 1] - R[:, 1, 2], R[:, 0, 2] - R[:, 2, 0], R[:, 1, 0] - R[:, 0, 1]], axis=1) / 2.0
+    return c, np.arctan2(np.sqrt((v * v).sum(1)), c)
 
 
 def nonfinite_case():

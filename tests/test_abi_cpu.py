@@ -57,6 +57,35 @@ def test_abi_declares_the_matcher_read_backs_with_the_headers_signatures(name):
     assert fn(*[None if a is ctypes.c_void_p else 0 for a in args]) == _abi.SFM_EINVAL
 
 
+def test_abi_declares_the_geometry_probe_with_the_headers_signature():
+    res, args = header_prototype("sfm_debug_geom")
+    assert _abi.GEOM_DEBUG_SIGNATURES["sfm_debug_geom"] == (res, args)
+    assert _native.SIGNATURES["sfm_debug_geom"] == (res, args)
+    text = open(HEADER).read()
+    ops = ("RODRIGUES", "RODRIGUES_INV", "EIG3", "NULL4", "COMPOSE", "ROTATE", "WAVE_SUM", "BLOCK_SUM")
+    for k, op in enumerate(ops):   # the op constants are the header's
+        assert re.search(rf"#define SFM_GEOM_{op} {k}\b", text), op
+        assert getattr(_abi, f"SFM_GEOM_{op}") == k
+    assert re.search(rf"#define SFM_GEOM_OPS {len(ops)}\b", text)
+    assert len(_abi.GEOM_ROW_IN) == len(_abi.GEOM_ROW_OUT) == len(ops)
+    # argument errors come back before any device call; n == 0 succeeds without one
+    fn = _native.load_library().sfm_debug_geom
+    buf = np.zeros(512, np.float64)
+    p = buf.ctypes.data
+    assert fn(0, 0, None, 1, p) == _abi.SFM_EINVAL and fn(0, 0, p, 1, None) == _abi.SFM_EINVAL
+    assert fn(0, 0, p, -1, p) == _abi.SFM_EINVAL and fn(0, 0, p, _abi.SFM_GEOM_MAX_ROWS + 1, p) == _abi.SFM_EINVAL
+    assert fn(0, -1, p, 1, p) == _abi.SFM_EINVAL and fn(0, len(ops), p, 1, p) == _abi.SFM_EINVAL
+    for op in range(len(ops)):
+        assert fn(0, op, p, 0, p) == _abi.SFM_OK
+        assert _native.debug_geom(op, np.zeros((0, _abi.GEOM_ROW_IN[op]))).shape == (0, _abi.GEOM_ROW_OUT[op])
+    # the binding's own checks: float64, C-contiguous, the op's row width
+    for bad in (np.zeros((2, 3), np.float32), np.zeros((3, 2)).T, np.zeros((2, 4)), np.zeros(3)):
+        with pytest.raises(ValueError):
+            _native.debug_geom(_abi.SFM_GEOM_RODRIGUES, bad)
+    with pytest.raises(ValueError):
+        _native.debug_geom(8, np.zeros((1, 3)))
+
+
 def test_struct_layout_matches_header(tmp_path):
     """ctypes mirror == the C compiler's layout of sfm_params (offsets and size)."""
     import subprocess

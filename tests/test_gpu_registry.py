@@ -13,7 +13,9 @@ tests/test_gpu_structure.py); every figure is printed before its assertion.
             900; 0 on the sequence case's prepare_for_ba output), bound 2.001e-13.  The device
             mean is 4.0e-15 / 3.3e-15 from the reference's recorded means.
 (On the CPU the restatement is 1.4e-15 from the same formula in extended precision under the
-first measure, and its mean 3.0e-15 from the reference's.)"""
+first measure, and its mean 3.0e-15 from the reference's.)
+ring9's tables (nine cameras from -pi to pi, 192 observations): errors 3.610e-16, mean 2.772e-16;
+with two camera vectors a whole turn off their principal form (|w| up to 8.63) 5.967e-16 and 0."""
 from __future__ import annotations
 
 import ctypes
@@ -244,3 +246,31 @@ def test_total_reprojection_error(k):
 def test_total_reprojection_error_of_nothing_is_nan():
     cam, pt, obs, cp, X, K = RR.score_case()
     assert np.isnan(pose.PointRegistry().total_reprojection_error(0, cam, pt, obs, cp, X, K))
+
+
+def test_total_reprojection_error_at_the_angles_of_an_orbit():
+    """k_total_reproj's rodrigues on ring9's own tables (tests/ba_ref.py): nine cameras from -pi to
+    pi, six of them beyond pi / 2 (score_case stays within 0.35 rad), then the same cameras with two
+    start vectors a whole turn below and above their principal form.  The existing measures and
+    bounds."""
+    from tests import ba_ref as BR
+    rings = BR.ring_cases()
+    sc, nq = rings["ring9"], rings["ring9_nonprincipal"]
+    M = len(sc["obs"])
+    assert M == 192
+    th = np.sqrt((sc["cams"][:, :3] ** 2).sum(1))
+    assert (th > np.pi / 2).sum() >= 6 and th.max() > 3.13
+    rest = RR.reprojection_errors(M, sc["cam_idx"], sc["pt_idx"], sc["obs"], sc["cams"], sc["X"], sc["K"])
+    scale = rest + np.linalg.norm(sc["obs"], axis=1)
+    rm = rest.sum() / M
+    for name, cams in (("ring9", sc["cams"]), ("ring9_nonprincipal", nq["cams"])):
+        info = {}
+        mean = pose.PointRegistry().total_reprojection_error(M, sc["cam_idx"], sc["pt_idx"], sc["obs"], cams, sc["X"],
+                                                             sc["K"], info=info)
+        err = info["errors"]
+        assert err.shape == (M,) and err.dtype == np.float64
+        d = float((np.abs(err - rest) / scale).max())     # the non-principal run against the principal restatement too
+        dm = abs(mean - rm) / rm
+        print(f"MEASURED score {name}: {M} observations, |w| up to {np.sqrt((cams[:, :3] ** 2).sum(1)).max():.4f}: errors vs "
+              f"restatement {d:.3e}, mean {mean:.12g} vs restatement {dm:.3e}")
+        assert d <= ERR_TOL and dm <= MEAN_TOL
