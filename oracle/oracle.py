@@ -109,6 +109,16 @@ def harris_response(img, params: dict | None = None):
     return R
 
 
+def harris_response_taps(img, taps, alpha: float):
+    """orc_harris_response with the window's taps given as they are (any square float32 kernel,
+    symmetric or not) instead of the Gaussian of a parameter set."""
+    img, taps = _c32(img), _c32(taps)
+    assert taps.ndim == 2 and taps.shape[0] == taps.shape[1]
+    R = np.empty_like(img)
+    lib().orc_harris_response(_f(img), img.shape[0], img.shape[1], _f(taps), taps.shape[0], float(alpha), _f(R))
+    return R
+
+
 def median(R) -> np.float32:
     R = _c32(R)
     return np.float32(lib().orc_median(_f(R), R.size))

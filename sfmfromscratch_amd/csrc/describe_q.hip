@@ -55,15 +55,22 @@ SFM_DEV double pi_edge(int i, int num) {  // numpy.linspace(-pi, pi, num)[i]
 
 // fkey of the smallest float o with fl((double)o - sh) >= e (or > e when `strict`): for
 // float keys v, (double)v - sh < e  <=>  fkey(v) < result, since the map is monotone.
+// Bisection over every float's key, not a walk from (float)(e + sh): where e + sh is 0 (the
+// cell edges +-pi/4, +-3pi/4 against the dominant orientations -+pi/4, -+3pi/4) the floats
+// whose difference rounds to e reach from -2^-54 (-2^-52 at 3pi/4) up to 0, ~10^9 keys, and a
+// walk of 64 steps stopped at the first denormals, which put orientations between there and
+// -2^-143 one bin low (tests/test_gpu_extract_variants.py, the merged-angle frame at width 6).
 SFM_DEV uint32_t edge_key(double e, double sh, bool strict) {
-  uint32_t kc = fkey((float)(e + sh));
   auto pass = [&](uint32_t kk) {
     const double d = (double)fkey_inv(kk) - sh;
     return strict ? d > e : d >= e;
   };
-  for (int it = 0; it < 64 && pass(kc); ++it) --kc;
-  for (int it = 0; it < 64 && !pass(kc); ++it) ++kc;
-  return kc;
+  uint32_t lo = fkey(-INFINITY), hi = fkey(INFINITY);  // pass(lo) is false, pass(hi) true
+  while (hi - lo > 1u) {
+    const uint32_t mid = lo + (hi - lo) / 2u;
+    if (pass(mid)) hi = mid; else lo = mid;
+  }
+  return hi;
 }
 
 // Bin-edge keys, the same for every keypoint, computed once per device by the host (the same
@@ -632,14 +639,16 @@ double pi_edge_h(int i, int num) {  // = dq::pi_edge
   return (double)i * step + start;
 }
 uint32_t edge_key_h(double e, double sh, bool strict) {  // = dq::edge_key
-  uint32_t kc = fkey_h((float)(e + sh));
   auto pass = [&](uint32_t kk) {
     const double d = (double)fkey_inv_h(kk) - sh;
     return strict ? d > e : d >= e;
   };
-  for (int it = 0; it < 64 && pass(kc); ++it) --kc;
-  for (int it = 0; it < 64 && !pass(kc); ++it) ++kc;
-  return kc;
+  uint32_t lo = fkey_h(-INFINITY), hi = fkey_h(INFINITY);  // pass(lo) is false, pass(hi) true
+  while (hi - lo > 1u) {
+    const uint32_t mid = lo + (hi - lo) / 2u;
+    if (pass(mid)) hi = mid; else lo = mid;
+  }
+  return hi;
 }
 }  // namespace
 

@@ -85,6 +85,20 @@ def tie_permutation(x_ref, y_ref, x, y, conf):
     return perm
 
 
+def tiny_orientation_windows(img, X, Y, fw):
+    """ok[i]: keypoint i's window (rows y-h+1 .. y+h, columns x-h+1 .. x+h, h = fw // 2) holds an
+    orientation with 0 < |ori| < 2^-25, the case in which k_describe_q orders a cell's pixels by
+    the exact float64 relative angle (describe_q.hip grp_tiny).  Orientations are the oracle's
+    Sobel gradients through np.arctan2."""
+    from oracle import oracle as O
+    sx = np.array([[-1, 0, 1], [-2, 0, 2], [-1, 0, 1]], np.float32)
+    sy = np.array([[-1, -2, -1], [0, 0, 0], [1, 2, 1]], np.float32)
+    ori = np.arctan2(O.filter2d(img, sy), O.filter2d(img, sx))
+    tiny = (ori != 0) & (np.abs(ori) < 2.0 ** -25)
+    h = int(fw) // 2
+    return np.array([bool(tiny[y - h + 1:y + h + 1, x - h + 1:x + h + 1].any()) for x, y in zip(X, Y)])
+
+
 def assert_matches_equal(m_ref, c_ref, m, c):
     """Matches identical; runs of equal nndr compared as sets (argsort unstable)."""
     m_ref = np.asarray(m_ref).reshape(-1, 2)

@@ -64,10 +64,46 @@ def test_certified_nms_stream_and_tile_vs_numpy(B, H, W, quantile):
             assert np.array_equal(got[b], want[b]), (tile, b)
 
 
-@pytest.mark.parametrize("ksize", [1, 5, 7])
+def ring_planes(H, W, kh):
+    """Planes on which the outermost row and column of the window decide: over a flat -1
+    background (below the threshold 0), sites of one pixel A (value 1 + site) and one larger
+    pixel B (100 + site) at offset r x (sy, sx) from it, for the eight directions and r = kh
+    (B is on the window's border: A is suppressed) and r = kh + 1 (just outside: A stays).
+    Sites sit 2 kh + 3 columns apart, so no site's pixels lie in another's windows.  A random
+    plane almost never notices a window one row or column short at ksize 31; this one must."""
+    offs = [(sy * r, sx * r) for r in (kh, kh + 1)
+            for sy, sx in ((-1, -1), (-1, 0), (-1, 1), (0, -1), (0, 1), (1, -1), (1, 0), (1, 1))]
+    per, ay = W // (2 * kh + 3), H // 2
+    assert per >= 1 and ay - (kh + 1) >= 0 and ay + kh + 1 < H
+    out = np.full((-(-len(offs) // per), H, W), -1.0, np.float32)
+    for s, (dy, dx) in enumerate(offs):
+        ax = kh + 1 + (s % per) * (2 * kh + 3)
+        out[s // per, ay, ax] = 1.0 + s
+        out[s // per, ay + dy, ax + dx] = 100.0 + s
+    return out
+
+
+@pytest.mark.parametrize("ksize", [1, 5, 7, 9, 11, 13, 21, 31])
 def test_certified_nms_other_window_sizes_vs_numpy(ksize):
-    R = planes(2, 45, 120, seed=ksize)
-    tnms = np.array([np.quantile(fkey(R[b]).astype(np.float64), 0.8) for b in range(2)]).astype(np.uint32)
-    got = _native.debug_nms(R, tnms, ksize=ksize)
-    for b in range(2):
-        assert np.array_equal(got[b], numpy_candidates(R[b], int(tnms[b]), ksize)), b
+    """k_nms_tile<0>, <2>, <3>, <4> (ksize 9) and k_nms_generic (11 and above, up to the largest
+    the context accepts); on 33 x 102 (W % 4 != 0) ksize 13 and above exceed a third of the
+    plane's height, so every window is clipped by an edge.  Two random planes and, for windows
+    wider than one pixel, the ring planes."""
+    for H, W in ((45, 120), (33, 102)):
+        R = planes(2, H, W, seed=ksize)
+        tnms = np.array([np.quantile(fkey(R[b]).astype(np.float64), 0.8) for b in range(2)]).astype(np.uint32)
+        if ksize > 1:
+            ring = ring_planes(H, W, ksize // 2)
+            R = np.concatenate([R, ring])
+            tnms = np.concatenate([tnms, np.full(len(ring), fkey(np.zeros(1, np.float32))[0], np.uint32)])
+        got = _native.debug_nms(R, tnms, ksize=ksize)
+        kept_a = 0
+        for b in range(len(R)):
+            want = numpy_candidates(R[b], int(tnms[b]), ksize)
+            assert np.array_equal(got[b], want), (H, W, b)
+            if b >= 2:
+                v = R[b].ravel()[(want & np.uint64(0xFFFFFFFF)).astype(np.int64)]
+                kept_a += int(((v >= 1) & (v < 100)).sum())
+        # the design holds: the eight A pixels with B just outside the window stay, the eight
+        # with B on its border do not
+        assert ksize == 1 or kept_a == 8
