@@ -170,6 +170,16 @@ int32_t sfm_resize_dims(int32_t H, int32_t W, double scale, int32_t* H2, int32_t
  * n_out their count; n_out = -1 when n < 8 (the reference returns four Nones), 0 when
  * iters == 0 (the reference's empty arrays).  No limit on n.
  * best_iter (optional): the winning sample's index.
+ * Each sample's F is the null vector of its normalised 8 x 9 system by Gaussian elimination
+ * with partial pivoting: for a rank-8 system the line of the reference's smallest right
+ * singular vector (epipolar distances within 1e-6 px of the reference's definition, DESIGN.md
+ * section 13).  A sample whose system is exactly rank-deficient (identical frames, a repeated
+ * correspondence, a constant coordinate) gets one finite member of its null space: the last
+ * column without a pivot set to 1, the other free columns to 0, the pivots back-substituted.
+ * The reference's SVD returns another member (LAPACK's choice, not reproduced), so the two may
+ * keep different points of such a pair beyond those that every member keeps.  F is NaN, and
+ * the sample counts no inlier, only when its eight points coincide in one image (the
+ * reference raises there).
  */
 int32_t sfm_ransac_find_inliers(sfm_ctx* ctx, const int64_t* p1, const int64_t* p2, int64_t n, int32_t iters,
                                 double threshold, int64_t* in1, int64_t* in2, int64_t* n_out,
@@ -722,6 +732,15 @@ int32_t sfm_debug_select_stats(sfm_ctx* ctx, int32_t* fallback_planes, int32_t* 
  * (R2, T), (R2, -T), or -1 (none valid, or the sample had no inlier and was skipped).
  * entries must be that call's P * iters (else SFM_ESTATE). */
 int32_t sfm_debug_pose_candidates(sfm_ctx* ctx, int32_t* cand_idx, int64_t entries);
+/* The per-sample fits of the last sfm_ransac_find_inliers* or sfm_ransac_camera_motion* call on
+ * this context (host outputs; synchronises the device): F [P][iters][9], each sample's
+ * fundamental matrix row-major as the count and selection kernels read it, and counts
+ * [P][iters], its inlier count — after a pose call the count that the cheirality check has
+ * zeroed for a sample without a valid candidate.  A copy of the workspaces; nothing is
+ * recomputed.  Entries of a pair with n < 8 are unspecified (no kernel writes its F).  entries
+ * must be that call's P * iters (else SFM_ESTATE; a single-pair host call with n < 8 runs
+ * nothing and counts as 0 entries); SFM_EINVAL for a null pointer or entries < 0. */
+int32_t sfm_debug_ransac_fits(sfm_ctx* ctx, double* F, int32_t* counts, int64_t entries);
 /* Level l's R maps (what 0) or level images (what 1) of the last extraction -> out [B][h][w]
  * (device, on `stream`; diagnostics). */
 int32_t sfm_debug_copy_level(sfm_ctx* ctx, int32_t l, int32_t what, float* out, void* stream);

@@ -62,6 +62,7 @@ SIGNATURES = {
                                                   _i32p]),
     "sfm_triangulate_dev": (ctypes.c_int32, [_vp, _vp, _vp, ctypes.c_int64, _vp, _vp, ctypes.c_int32, _vp, _vp]),
     "sfm_debug_pose_candidates": (ctypes.c_int32, [_vp, _i32p, ctypes.c_int64]),
+    "sfm_debug_ransac_fits": (ctypes.c_int32, [_vp, _dp, _i32p, ctypes.c_int64]),
     "sfm_refine_points_dev": (ctypes.c_int32, [_vp, _vp, _vp, _vp, ctypes.c_int64, _vp, ctypes.c_int32, _vp,
                                                ctypes.c_int32, _vp, _vp, _vp, _vp]),
     "sfm_reprojection_error_dev": (ctypes.c_int32, [_vp, _vp, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp]),
@@ -383,6 +384,14 @@ class Context:
         out = np.empty((P, iters), np.int32)
         check(self.lib.sfm_debug_pose_candidates(self.handle, out.ctypes.data_as(_i32p), P * iters), self.handle)
         return out
+
+    def ransac_fits(self, P: int, iters: int):
+        """(F [P, iters, 3, 3] float64, counts [P, iters] int32) of the last RANSAC or pose call."""
+        F = np.empty((P, iters, 3, 3), np.float64)
+        counts = np.empty((P, iters), np.int32)
+        check(self.lib.sfm_debug_ransac_fits(self.handle, F.ctypes.data_as(_dp), counts.ctypes.data_as(_i32p),
+                                             P * iters), self.handle)
+        return F, counts
 
     # -------- device-pointer API (throughput path; pointers are ints) --------
     def ingest_rgb_dev(self, rgb_ptr: int, B: int, H: int, W: int, H2: int, W2: int, gray_ptr: int,

@@ -141,6 +141,7 @@ int ransac_impl(sfm_ctx* c, const int32_t* pts, const int32_t* npts_dev, const i
   if ((rc = ensure(c, r.counts, (size_t)P * std::max(iters, 1) * 4))) return rc;
   HIPCHK(c, hipMemcpyAsync(r.idx.p, all.data(), all.size() * 4, hipMemcpyHostToDevice, st));
   HIPCHK(c, hipMemcpyAsync(r.off.p, off.data(), (size_t)P * 4, hipMemcpyHostToDevice, st));
+  r.last_entries = (int64_t)P * iters;
   if (pose) {
     PoseWs& w = c->pose;
     const size_t slots = (size_t)P * std::max(iters, 1);
@@ -182,7 +183,10 @@ int ransac_host_pair(sfm_ctx* c, const int64_t* p1, const int64_t* p2, int64_t n
   if (n > INT32_MAX / 4) return set_err(c, SFM_EINVAL, "too many correspondences");
   HIPCHK(c, hipSetDevice(c->device));
   *n_out = -1;
-  if (n < 8) return SFM_OK;  // the reference returns (None, None, None, None)
+  if (n < 8) {  // the reference returns (None, None, None, None); nothing ran: no fits to read back
+    c->ransac.last_entries = 0;
+    return SFM_OK;
+  }
   const int nmax = (int)n;
   std::vector<int32_t> h((size_t)nmax * 4);
   for (int64_t i = 0; i < n; ++i) {
@@ -331,6 +335,16 @@ int32_t sfm_debug_pose_candidates(sfm_ctx* c, int32_t* cand_idx, int64_t entries
   if (entries == 0) return SFM_OK;
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipMemcpy(cand_idx, c->pose.cand_idx.p, (size_t)entries * 4, hipMemcpyDeviceToHost));
+  return SFM_OK;
+}
+
+int32_t sfm_debug_ransac_fits(sfm_ctx* c, double* F, int32_t* counts, int64_t entries) {
+  if (!c || !F || !counts || entries < 0) return SFM_EINVAL;
+  if (entries != c->ransac.last_entries) return set_err(c, SFM_ESTATE, "not the last RANSAC call's P * iters");
+  if (entries == 0) return SFM_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpy(F, c->ransac.F.p, (size_t)entries * 9 * 8, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(counts, c->ransac.counts.p, (size_t)entries * 4, hipMemcpyDeviceToHost));
   return SFM_OK;
 }
 

@@ -156,6 +156,7 @@ struct IngestWs {
 struct RansacWs {
   std::vector<std::pair<std::pair<int, int>, std::vector<int32_t>>> cache;
   DevBuf idx, off, F, counts, pts, npts, out, on, oit;
+  int64_t last_entries = 0;  // P * iters of the last call (sfm_debug_ransac_fits)
 };
 
 // Pose (sfm_ransac_camera_motion*, sfm_triangulate_dev): per-pair intrinsics and base pose,

@@ -35,15 +35,15 @@ def case(z, name):
 
 
 def run(z, name):
-    """The single-pair host call and its per-iteration candidate table."""
+    """The single-pair host call, its per-iteration candidate table and its per-iteration counts."""
     p1, p2, K1, K2, Rb, Tb, thr, iters = case(z, name)
     ctx = _native.context_for(_abi.params_from_dict({}, _abi.SFM_MODE_NAIVE))
     r = ctx.ransac_camera_motion(p1, p2, K1, K2, Rb, Tb, thr, iters)
-    return r, ctx.pose_candidates(1, iters)[0]
+    return r, ctx.pose_candidates(1, iters)[0], ctx.ransac_fits(1, iters)[1][0]
 
 
 def check_pose(z, name):
-    (R, t, in1, in2, it), cand = run(z, name)
+    (R, t, in1, in2, it), cand, counts = run(z, name)
     assert it == int(z[f"{name}_win"])
     assert np.array_equal(in1, z[f"{name}_in1"]) and np.array_equal(in2, z[f"{name}_in2"])
     dR, dt = np.abs(R - z[f"{name}_R"]).max(), np.abs(t - z[f"{name}_t"]).max()
@@ -52,6 +52,8 @@ def check_pose(z, name):
     # per iteration: some candidate valid (iterations without an inlier are skipped: -1)
     want = z[f"{name}_valid"].any(axis=1) & (z[f"{name}_counts"] > 0)
     assert np.array_equal(cand >= 0, want)
+    # every sample's inlier count, zeroed where no candidate passed the cheirality check
+    assert np.array_equal(counts, np.where(z[f"{name}_valid"].any(axis=1), z[f"{name}_counts"], 0))
     # the public call: the same arrays with the input dtype
     p1, p2, K1, K2, Rb, Tb, thr, iters = case(z, name)
     r = pose.ransac_camera_motion(p1, p2, K1, K2, Rb, Tb, threshold=thr, max_iterations=iters)

@@ -1,7 +1,10 @@
 """GPU: the RANSAC consumer (ransac.hip, pose.find_inliers) against the reference's own
 CameraPose.find_inliers outputs (tests/golden/ransac.npz) and the oracle restatement.
-Bar: identical inlier arrays (float64 differences between LAPACK's SVD and the device's
-elimination could only move a point within ~1e-12 of the threshold)."""
+Bar: identical inlier arrays.  On general motion the device's and LAPACK's per-sample distances
+agree to 1e-6 px (tests/test_gpu_ransac_fits.py).  The planted sets below are pure image
+translations, whose 8 x 9 systems have numerical rank 6: there the two routes count different
+inliers in some samples (tests/test_ransac_ref_cpu.py) and only the winner, which has coincided
+on these inputs, is held; their general-motion twins are in tests/test_gpu_ransac_fits.py."""
 from __future__ import annotations
 
 import numpy as np

@@ -150,3 +150,7 @@ def test_new_calls_reject_bad_arguments_without_a_device():
     assert L.sfm_debug_pose_candidates(None, i32, 0) == E
     assert L.sfm_debug_pose_candidates(fake, None, 0) == E
     assert L.sfm_debug_pose_candidates(fake, i32, -1) == E
+    assert L.sfm_debug_ransac_fits(None, d, i32, 0) == E
+    assert L.sfm_debug_ransac_fits(fake, None, i32, 0) == E
+    assert L.sfm_debug_ransac_fits(fake, d, None, 0) == E
+    assert L.sfm_debug_ransac_fits(fake, d, i32, -1) == E

@@ -425,6 +425,18 @@ def gen_ransac():
     save("ransac.npz", **out)
 
 
+def gen_ransac_fits():
+    """Every sample's F by the reference's definition in 60 digits (tests/ransac_ref.py, mpmath),
+    the inputs of the degenerate-motion pairs and the branch samples of the elimination.  The
+    arithmetic is mpmath's and the container has constant timestamps: the same bytes every run."""
+    from tests import ransac_ref as RR
+    t0 = time.time()
+    data = RR.fixture_bytes(RR.fixture_arrays(progress=lambda s: print("  " + s)))
+    with open(os.path.join(OUT, "ransac_fits.npz"), "wb") as f:
+        f.write(data)
+    print(f"  wrote ransac_fits.npz ({len(data) / 1024:.0f} KiB, {time.time() - t0:.0f} s)")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--skip-1080p", action="store_true")
@@ -441,6 +453,7 @@ def main():
         "match": gen_match,
         "ingest": gen_ingest,
         "ransac": gen_ransac,
+        "ransac_fits": gen_ransac_fits,
         "small": lambda: (gen_extract("extract_small_scalerot.npz", 150, 200, 21, P_OCT, "scalerot"),
                           gen_extract("extract_small_pmain.npz", 151, 203, 22, P_MAIN, "scalerot"),
                           gen_extract("extract_small_naive.npz", 150, 200, 23, {"num_interest_points": 500},
