@@ -711,11 +711,18 @@ int64_t sfm_debug_match_stamps(uint64_t* out, int64_t cap);
  * h at [128 h ...): target index in the low 16 bits, d~ rounded down to bfloat16 in the high
  * 16.  Rows at or beyond the pair's first count, and every row of a pair whose second image is
  * empty, are not written.  SFM_ESTATE when that call ran as more than one sub-launch (the
- * workspaces then hold the last one only) or no call was made; SFM_EINVAL for pair outside it. */
+ * workspaces then hold the last one only) or no call was made; SFM_EINVAL for pair outside it.
+ *
+ * sfm_debug_match_skips: of the same pair and rows, with the same argument and state rules,
+ * skip [rows]: 1 for a row the sweep proved to fail the ratio test from its two smallest d~ and
+ * E alone (the sweep wrote its "no match"; the exact re-rank never saw the row), else 0.
+ * A row handed to the exact kernel is never flagged.  The rows sfm_debug_match_windows leaves
+ * unwritten are unwritten here too. */
 int32_t sfm_debug_match_operands(sfm_ctx* ctx, int32_t slot, int64_t rows, uint16_t* hi, uint16_t* lo,
                                  float* norm2, float* rnorm, float* pmax);
 int32_t sfm_debug_match_windows(sfm_ctx* ctx, int32_t pair, int64_t rows, int32_t* cand_n, float* cand_thr,
                                 uint32_t* cand);
+int32_t sfm_debug_match_skips(sfm_ctx* ctx, int32_t pair, int64_t rows, uint8_t* skip);
 
 /* Exchange emulation for a single-GPU rehearsal of the multi-GPU job (bench.py
  * --emulate-exchange): copy `bytes` from src to dst (device pointers, 16-B aligned) on

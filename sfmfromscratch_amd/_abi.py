@@ -53,6 +53,8 @@ MATCH_DEBUG_SIGNATURES = {
     "sfm_debug_match_operands": (ctypes.c_int32, [_vp, ctypes.c_int32, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp]),
     # ctx, pair, rows, cand_n, cand_thr, cand
     "sfm_debug_match_windows": (ctypes.c_int32, [_vp, ctypes.c_int32, ctypes.c_int64, _vp, _vp, _vp]),
+    # ctx, pair, rows, skip
+    "sfm_debug_match_skips": (ctypes.c_int32, [_vp, ctypes.c_int32, ctypes.c_int64, _vp]),
 }
 # include/sfmfeat.h's probe of the geometry kernels' shared float64 helpers (host pointers as void*;
 # tests/test_abi_cpu.py holds it against the header's prototype): device, op, in, n, out

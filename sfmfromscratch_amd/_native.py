@@ -107,7 +107,7 @@ SIGNATURES = {
     "sfm_debug_harris_stamps": (ctypes.c_float, [ctypes.c_int32] * 6 + [ctypes.c_void_p, ctypes.c_int64]),
     "sfm_debug_match_stamps": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int64]),
     "sfm_debug_select_stats": (ctypes.c_int32, [_vp, _i32p, _i32p]),
-    **_abi.MATCH_DEBUG_SIGNATURES,  # sfm_debug_match_operands, sfm_debug_match_windows
+    **_abi.MATCH_DEBUG_SIGNATURES,  # sfm_debug_match_operands, sfm_debug_match_windows, sfm_debug_match_skips
     **_abi.GEOM_DEBUG_SIGNATURES,  # sfm_debug_geom
     "sfm_copy_wg": (ctypes.c_int32, [_vp, _vp, ctypes.c_int64, ctypes.c_int32, _vp]),
     "sfm_dist_unique_id": (ctypes.c_int32, [_u8p]),
@@ -481,6 +481,14 @@ class Context:
         check(self.lib.sfm_debug_match_windows(self.handle, int(pair), rows, cn.ctypes.data, ct.ctypes.data,
                                                cd.ctypes.data), self.handle)
         return cn, ct, cd
+
+    def match_skips(self, pair: int, rows: int):
+        """sfm_debug_match_skips of pair `pair` of the last match call on this context -> skip [rows]
+        uint8: 1 for a row the sweep proved unmatched (the re-rank never read its window)."""
+        rows = int(rows)
+        sk = np.empty(max(rows, 1), np.uint8)
+        check(self.lib.sfm_debug_match_skips(self.handle, int(pair), rows, sk.ctypes.data), self.handle)
+        return sk
 
     # -------- feature tracks (tensors, checked: the C ABI sees only addresses) --------
     def _tensor_ptr(self, t, dtype: str, numel: int, what: str, optional: bool = False):

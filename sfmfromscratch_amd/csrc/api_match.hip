@@ -111,11 +111,14 @@ int match_impl(sfm_ctx* c, const float* desc, const int32_t* count, int nimg, in
   // admitted targets per query row: 512 B per row) is bounded: large P runs as consecutive
   // sub-launches over a fixed budget (SFMFEAT_MATCH_BUDGET_MB, default 4096 = 4 GiB) instead
   // of one allocation that grows with P * cap.
-  const size_t per_pair = (size_t)cap * (sizeof(RowBest) + sizeof(int2) + (m.direct ? 0 : kMatchCandCap * 4 + 8));
+  const size_t per_pair = (size_t)cap * (sizeof(RowBest) + sizeof(int2) + (m.direct ? 0 : kMatchCandCap * 4 + 13));
   // (at most 2^kMatchUnitPairBits pairs per sub-launch: the sweep's work units hold the pair
-  // index in that many bits, so a small capacity under a large budget cannot wrap it)
+  // index in that many bits, so a small capacity under a large budget cannot wrap it; and
+  // fewer than 2^31 (pair, row) slots: the re-rank's work list holds them in 32 bits)
   const int Pmax = (int)std::max<size_t>(
-      1, std::min<size_t>(std::min<size_t>((size_t)P, m.budget / per_pair), (size_t)1 << kMatchUnitPairBits));
+      1, std::min<size_t>(std::min<size_t>(std::min<size_t>((size_t)P, m.budget / per_pair),
+                                           (size_t)1 << kMatchUnitPairBits),
+                          (size_t)0x7fffffff / (size_t)cap));
   if ((rc = ensure(c, m.rows, (size_t)Pmax * cap * sizeof(RowBest)))) return rc;
   if ((rc = ensure(c, m.ovf, (size_t)Pmax * cap * sizeof(int2)))) return rc;
   if (m.ovfc.bytes == 0) {  // the overflow counter starts at zero; k_match_compact re-zeroes it
@@ -126,6 +129,8 @@ int match_impl(sfm_ctx* c, const float* desc, const int32_t* count, int nimg, in
     if ((rc = ensure(c, m.cand, (size_t)Pmax * cap * kMatchCandCap * 4))) return rc;
     if ((rc = ensure(c, m.candn, (size_t)Pmax * cap * 4))) return rc;
     if ((rc = ensure(c, m.candt, (size_t)Pmax * cap * 4))) return rc;
+    if ((rc = ensure(c, m.cands, (size_t)Pmax * cap))) return rc;  // one flag byte per row (proven unmatched)
+    if ((rc = ensure(c, m.work, (size_t)Pmax * cap * 4))) return rc;  // the re-rank's work list: (pair, row) items
     if ((rc = ensure(c, m.units, match_units_words(Pmax, (int)cap) * 4))) return rc;
   }
   const int64_t capP = operand_rows(c, cap);
@@ -143,8 +148,8 @@ int match_impl(sfm_ctx* c, const float* desc, const int32_t* count, int nimg, in
       else if (!(m.calls > 0 && skip_sweep))
         launch_match_mfma(desc, count, cap, capP, as<_Float16>(o.hi), as<_Float16>(o.lo), as<float>(o.norm2),
                           as<float>(o.rnorm), o.imgmax.p, pr, Pn, ratio, as<RowBest>(m.rows), (int)cap,
-                          as<uint32_t>(m.cand), as<int32_t>(m.candn), as<float>(m.candt), as<int>(m.ovfc),
-                          as<int2>(m.ovf), as<int32_t>(m.units), st);
+                          as<uint32_t>(m.cand), as<int32_t>(m.candn), as<float>(m.candt), as<uint8_t>(m.cands),
+                          as<uint32_t>(m.work), as<int>(m.ovfc), as<int2>(m.ovf), as<int32_t>(m.units), st);
     }
     {
       StageScope sc(c, SFM_PROF_MATCH_POST, st);
@@ -289,6 +294,21 @@ int32_t sfm_debug_match_windows(sfm_ctx* c, int32_t pair, int64_t rows, int32_t*
   HIPCHK(c, hipMemcpy(cand_n, as<int32_t>(m.candn) + r0, n * 4, hipMemcpyDeviceToHost));
   HIPCHK(c, hipMemcpy(cand_thr, as<float>(m.candt) + r0, n * 4, hipMemcpyDeviceToHost));
   HIPCHK(c, hipMemcpy(cand, as<uint32_t>(m.cand) + r0 * kMatchCandCap, n * kMatchCandCap * 4, hipMemcpyDeviceToHost));
+  return SFM_OK;
+}
+
+int32_t sfm_debug_match_skips(sfm_ctx* c, int32_t pair, int64_t rows, uint8_t* skip) {
+  if (!c || !skip || pair < 0 || rows < 1) return SFM_EINVAL;
+  MatchWs& m = c->match;
+  if (m.direct) return set_err(c, SFM_ESTATE, "the direct matcher keeps no windows");
+  if (m.last_subs != 1)
+    return set_err(c, SFM_ESTATE, m.last_subs ? "the last match call ran as more than one sub-launch"
+                                              : "no match call on this context yet");
+  if (pair >= m.last_P || rows > m.last_cap) return set_err(c, SFM_EINVAL, "pair or rows outside the last match call");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipDeviceSynchronize());
+  HIPCHK(c, hipMemcpy(skip, as<uint8_t>(m.cands) + (size_t)pair * (size_t)m.last_cap, (size_t)rows,
+                      hipMemcpyDeviceToHost));
   return SFM_OK;
 }
 

@@ -129,7 +129,7 @@ struct MatchOperandsWs {
 
 struct MatchWs {
   MatchOperandsWs ops;
-  DevBuf rows, ovf, ovfc, cand, candn, candt, units;   // per pair, bounded by `budget`
+  DevBuf rows, ovf, ovfc, cand, candn, candt, cands, work, units;   // per pair, bounded by `budget`
   DevBuf h_desc, h_count, h_pairs, h_matches, h_conf, h_nmatch;  // sfm_match's two-slot table
   bool fused_prep = false;
   bool direct = false;  // SFMFEAT_MATCH_DIRECT=1: all-pairs exact VALU kernel (A/B checks)

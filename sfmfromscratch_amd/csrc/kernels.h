@@ -488,6 +488,7 @@ void launch_match_mfma(const float* desc, const int32_t* count, int64_t cap, int
                        const _Float16* hi, const _Float16* lo, const float* norm2, const float* rnorm,
                        const void* pmax, const int32_t* pairs, int P, float ratio,
                        RowBest* rows, int max_rows, uint32_t* cand, int32_t* cand_n, float* cand_thr,
-                       int* ovf_count, int2* ovf_list, int32_t* units, hipStream_t st);
+                       uint8_t* cand_skip, uint32_t* work_list, int* ovf_count, int2* ovf_list, int32_t* units,
+                       hipStream_t st);
 
 }  // namespace sfm

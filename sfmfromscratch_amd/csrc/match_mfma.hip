@@ -12,6 +12,8 @@
 //      f32 accumulation error, f32 rounding of d~ and of the reference's own pairwise
 //      sum); any target outside the final window is strictly farther than the second
 //      nearest (argument above k_match_mfma);
+//      a row it can prove unmatched from its two smallest d~ and E (proven_unmatched) gets
+//      its "no match" there; the other rows go to the re-rank's work list;
 //   2. k_match_rerank: the list entries within the row's final threshold recomputed with the
 //      reference's exact float32 pairwise order (8 accumulators), (distance, index) top-2,
 //      ratio test;
@@ -166,6 +168,24 @@ SFM_DEV void top2_merge(float& b1, int& j1, float& b2, float ob1, int oj1, float
   }
 }
 
+// The sweep's certificate that a row fails the ratio test ("Rows the prefilter
+// proves unmatched").  r1 <= r2: the row's two smallest d~ over every target; E2 = 2E, finite.
+// Every target's exact distance is within E of its d~, so the exact smallest is >= r1 - E and
+// the exact second smallest <= r2 + E (two targets lie at or below it).  L and U are those two
+// bounds moved one ulp outward on the float bits (the subtraction and the addition each round
+// once).  sqrtf and / below are the re-rank's own, correctly rounded and so monotone: the
+// re-rank's nndr >= t, and t > ratio means the row has no match.  U = +inf (fewer than two
+// targets, or an overflowing sum) and NaN prove nothing.
+SFM_DEV bool proven_unmatched(float r1, float r2, float E2, float ratio) {
+  const float E = 0.5f * E2;
+  float L = fmaxf(r1 - E, 0.0f);
+  if (L > 0.0f) L = __uint_as_float(__float_as_uint(L) - 1u);
+  float U = r2 + E;
+  if (U >= 0.0f) U = __uint_as_float((__float_as_uint(U) & 0x7fffffffu) + 1u);  // +inf -> NaN
+  const float t = sqrtf(L) / sqrtf(U);
+  return U > 0.0f && U < INFINITY && t > ratio;
+}
+
 constexpr int kTT2 = 64;               // targets per LDS stage (two 32-target MFMA sub-tiles)
 // LDS of one sweep workgroup (one __shared__ array; carved per staging form below): stage
 // buffers (hi, lo), target norms of the stages in use, the per-wave d~ staging of the appends:
@@ -250,7 +270,8 @@ __device__ __forceinline__ void glds_x1(const void* gsrc, uint32_t lds_dst) {
 // live on the device.)
 __global__ void __launch_bounds__(1024) k_match_units(const int32_t* __restrict__ count,
                                                       const int32_t* __restrict__ pairs, int P, int max_rows,
-                                                      int qbr, int32_t* __restrict__ units) {
+                                                      int qbr, int32_t* __restrict__ units,
+                                                      int* __restrict__ work_count) {
   __shared__ uint32_t s_w[16];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   uint32_t base = 0;
@@ -275,7 +296,10 @@ __global__ void __launch_bounds__(1024) k_match_units(const int32_t* __restrict_
     base += tot;
     __syncthreads();
   }
-  if (tid == 0) units[0] = (int32_t)base;
+  if (tid == 0) {
+    units[0] = (int32_t)base;
+    *work_count = 0;  // the re-rank's work list of this launch starts empty
+  }
 }
 
 // ABL & 32 (diagnostic build): per-wave shader-clock stamps of the first kStampSt stages of
@@ -294,7 +318,9 @@ __global__ void __launch_bounds__(64 * sweep_waves(STAGE), STAGE == 3 ? 2 : 1) k
     const _Float16* __restrict__ lo, const float* __restrict__ norm2, const float* __restrict__ rnorm,
     const float2* __restrict__ pmax, const int32_t* __restrict__ pairs, int P, int max_rows,
     uint32_t* __restrict__ cand, int32_t* __restrict__ cand_n, float* __restrict__ cand_thr,
-    int* __restrict__ ovf_count, int2* __restrict__ ovf_list, const int32_t* __restrict__ units) {
+    int* __restrict__ ovf_count, int2* __restrict__ ovf_list, const int32_t* __restrict__ units, float ratio,
+    uint8_t* __restrict__ cand_skip, RowBest* __restrict__ rows_out, int* __restrict__ work_count,
+    uint32_t* __restrict__ work_list) {
   constexpr bool DMA = STAGE >= 1;
   constexpr bool H3 = STAGE == 3;                // the half-CU form
   constexpr int NW = sweep_waves(STAGE), NTH = 64 * NW, QBR = sweep_rows(STAGE);
@@ -354,15 +380,19 @@ __global__ void __launch_bounds__(64 * sweep_waves(STAGE), STAGE == 3 ? 2 : 1) k
   const int ql = wid * kQW + (lane & 31);           // local query row 0..255
   const int qi = row0 + ql;                          // query row in image i1
   const int half = lane >> 5;
-  const int64_t qo = ((int64_t)i1 * capP + qi) * 128;
+  // capP is a multiple of 128, not of the 256-row block: the block's rows past capP (never
+  // live) read the slot's last row instead of the next slot's rows, or, in the table's last
+  // slot, memory past the end of the operand buffers
+  const int qr = min(qi, (int)capP - 1);
+  const int64_t qo = ((int64_t)i1 * capP + qr) * 128;
   h8 qhi[8], qlo[8];
 #pragma unroll
   for (int kk = 0; kk < 8; ++kk) {
     qhi[kk] = *reinterpret_cast<const h8*>(hi + qo + kk * 16 + 8 * half);
     qlo[kk] = *reinterpret_cast<const h8*>(lo + qo + kk * 16 + 8 * half);
   }
-  const float na = norm2[(int64_t)i1 * capP + qi];
-  const float ra = rnorm[(int64_t)i1 * capP + qi];
+  const float na = norm2[(int64_t)i1 * capP + qr];
+  const float ra = rnorm[(int64_t)i1 * capP + qr];
   // the target image's maxima of norm2 / norm: reduced here from k_match_prep's per-block
   // maxima (capP / kPrepRows of them), through the d~ staging area before its first use
   float maxn2, maxrn;
@@ -779,19 +809,43 @@ __global__ void __launch_bounds__(64 * sweep_waves(STAGE), STAGE == 3 ? 2 : 1) k
   // the row's final window threshold (both halves merged): the re-rank drops the admitted
   // targets above it (their stored d~ is rounded down, so no window member is dropped)
   const float ob1 = other_half(b1), ob2 = other_half(b2);
-  const float thr_final = fminf(fminf(fmaxf(b1, ob1), fminf(b2, ob2)) + E2, thr_w);
+  const float r2 = fminf(fmaxf(b1, ob1), fminf(b2, ob2));  // the row's second smallest d~
+  const float thr_final = fminf(r2 + E2, thr_w);
   const int ocnt = other_half(cnt);
   // a non-finite bound (k_match_prep flagged this row, or a row of the target image: an element
   // outside the f16 range; or the norms overflow float32): the window proves nothing, so the
   // row takes an over-cap count (the re-rank skips it) and the exact kernel
   const bool unbounded = !(E2 <= 3.0e38f);  // E2 = 2E, live to the end anyway
+  bool todo = false;  // a row for the exact re-rank
   if (live && half == 0) {
     cand_thr[(int64_t)p * max_rows + qi] = thr_final;
     cand_n[(int64_t)p * max_rows + qi] = unbounded ? 0x7fff : cnt | (ocnt << 16);  // n2 < 2^16 (kMaxMatchRows)
-    if (cnt > kHalfCap || ocnt > kHalfCap || unbounded) {  // exact over every target instead
+    const bool over = cnt > kHalfCap || ocnt > kHalfCap || unbounded;
+    if (over) {  // exact over every target instead
       const int k = atomicAdd(ovf_count, 1);
       ovf_list[k] = make_int2(p, qi);
     }
+    // a row proven to fail the ratio test gets its "no match" here and never reaches the
+    // re-rank (rows of the exact kernel are left to it)
+    const bool skip = !over && proven_unmatched(fminf(b1, ob1), r2, E2, ratio);
+    cand_skip[(int64_t)p * max_rows + qi] = skip ? 1 : 0;
+    if (skip) {
+      RowBest rb;
+      rb.col = -1;
+      rb.nndr = 0.0f;
+      rows_out[(int64_t)p * max_rows + qi] = rb;
+    }
+    todo = !over && !skip;
+  }
+  // the re-rank's work list: the rows left for it, appended with one atomic per wavefront (the
+  // order varies from run to run; every row's result is its own)
+  const uint64_t bal = __ballot(todo);
+  if (bal) {
+    const int lead = __ffsll((unsigned long long)bal) - 1;
+    int base = 0;
+    if (lane == lead) base = atomicAdd(work_count, __popcll(bal));
+    base = __shfl(base, lead);
+    if (todo) work_list[base + __popcll(bal & ((1ull << lane) - 1ull))] = (uint32_t)(p * max_rows + qi);
   }
 }
 
@@ -810,16 +864,19 @@ __global__ void __launch_bounds__(256) k_match_rerank(const float* __restrict__ 
                                                       int max_rows, const uint32_t* __restrict__ cand,
                                                       const int32_t* __restrict__ cand_n,
                                                       const float* __restrict__ cand_thr,
+                                                      const int* __restrict__ work_count,
+                                                      const uint32_t* __restrict__ work_list,
                                                       RowBest* __restrict__ rows_out) {
   __shared__ uint16_t sJ[4][kCandCap];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int grp = lane >> 3, l8 = lane & 7;
-  const int64_t w = (int64_t)blockIdx.x * 4 + wv;  // (pair, row)
+  // item t of the sweep's work list: a live row that is neither proven unmatched (the sweep
+  // wrote its "no match") nor the exact kernel's; the grid covers every (pair, row) slot
+  const int64_t t = (int64_t)blockIdx.x * 4 + wv;
+  if (t >= *work_count) return;
+  const int64_t w = work_list[t];  // (pair, row)
   const int p = (int)(w / max_rows), row = (int)(w % max_rows);
-  if (p >= P) return;
   const int i1 = pairs[2 * p], i2 = pairs[2 * p + 1];
-  const int n1 = count[i1], n2 = count[i2];
-  if (row >= n1 || n2 < 1) return;
   const int cw = cand_n[w];
   const int c0 = cw & 0xffff, c1 = cw >> 16;  // the two half-lists' lengths
   if (c0 > kHalfCap || c1 > kHalfCap) return;  // k_match_overflow's row
@@ -897,21 +954,21 @@ __global__ void __launch_bounds__(256) k_match_rerank2(const float* __restrict__
                                                        int max_rows, const uint32_t* __restrict__ cand,
                                                        const int32_t* __restrict__ cand_n,
                                                        const float* __restrict__ cand_thr,
+                                                       const int* __restrict__ work_count,
+                                                       const uint32_t* __restrict__ work_list,
                                                        RowBest* __restrict__ rows_out) {
   __shared__ uint16_t sJ[4][2][kCandCap];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, hf = lane >> 5, hl = lane & 31;
   const int grp = hl >> 3, l8 = lane & 7;
-  const int64_t w = ((int64_t)blockIdx.x * 4 + wv) * 2 + hf;  // (pair, row) of this half-wave
+  // items 2 i and 2 i + 1 of the sweep's work list (the live rows that are neither proven
+  // unmatched — the sweep wrote their "no match" — nor the exact kernel's); the grid covers
+  // every (pair, row) slot, and a wavefront beyond the list's end leaves at once
+  const int64_t t = ((int64_t)blockIdx.x * 4 + wv) * 2 + hf;
+  bool ok = t < *work_count;
+  if (!__any(ok)) return;
+  const int64_t w = ok ? (int64_t)work_list[t] : 0;  // (pair, row) of this half-wave
   const int p = (int)(w / max_rows), row = (int)(w % max_rows);
-  bool ok = p < P;
-  int i1 = 0, i2 = 0, n1 = 0, n2 = 0;
-  if (ok) {
-    i1 = pairs[2 * p];
-    i2 = pairs[2 * p + 1];
-    n1 = count[i1];
-    n2 = count[i2];
-    ok = row < n1 && n2 >= 1;
-  }
+  const int i1 = pairs[2 * p], i2 = pairs[2 * p + 1];
   int c0 = 0, c1 = 0;
   float thr = 0.0f;
   if (ok) {
@@ -1016,6 +1073,8 @@ __global__ void __launch_bounds__(256) k_match_rerank8(const float* __restrict__
                                                       int max_rows, const uint32_t* __restrict__ cand,
                                                       const int32_t* __restrict__ cand_n,
                                                       const float* __restrict__ cand_thr,
+                                                      const int* __restrict__ work_count,
+                                                      const uint32_t* __restrict__ work_list,
                                                       RowBest* __restrict__ rows_out) {
   __shared__ __attribute__((aligned(16))) float sA[4][kRrRows][128];  // query rows
   __shared__ uint16_t sL[4][kRrRows * kCandCap];  // window members (target index), row order
@@ -1023,25 +1082,24 @@ __global__ void __launch_bounds__(256) k_match_rerank8(const float* __restrict__
   __shared__ int sBeg[4][kRrRows + 1];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int grp = lane >> 3, l8 = lane & 7;
-  const int64_t total = (int64_t)P * max_rows;
-  const int64_t w0 = ((int64_t)blockIdx.x * 4 + wv) * kRrRows;  // first (pair, row) item
-  if (w0 >= total) return;
+  // items t0 .. t0 + 7 of the sweep's work list (the live rows that are neither proven
+  // unmatched nor the exact kernel's); a wavefront beyond the list's end leaves at once
+  const int64_t total = *work_count;
+  const int64_t t0 = ((int64_t)blockIdx.x * 4 + wv) * kRrRows;
+  if (t0 >= total) return;
   // 1. per-row state on lanes 0..7, then broadcast by shuffles
-  int c_l = 0, ok_l = 0, i1_l = 0, i2_l = 0, row_l = 0, p_l = 0;
+  int c_l = 0, ok_l = 0, w_l = 0, i1_l = 0, i2_l = 0, row_l = 0, p_l = 0;
   float thr_l = 0.0f;
   if (lane < kRrRows) {
-    const int64_t w = w0 + lane;
-    if (w < total) {
-      p_l = (int)(w / max_rows);
-      row_l = (int)(w % max_rows);
+    if (t0 + lane < total) {
+      w_l = (int)work_list[t0 + lane];  // (pair, row): below 2^31 (match_impl)
+      p_l = w_l / max_rows;
+      row_l = w_l % max_rows;
       i1_l = pairs[2 * p_l];
       i2_l = pairs[2 * p_l + 1];
-      const int n1 = count[i1_l], n2 = count[i2_l];
-      if (row_l < n1 && n2 >= 1) {
-        c_l = cand_n[w];  // half-list lengths, low / high 16 bits
-        thr_l = cand_thr[w];
-        ok_l = ((c_l & 0xffff) <= kHalfCap && (c_l >> 16) <= kHalfCap) ? 1 : 0;  // else k_match_overflow's row
-      }
+      c_l = cand_n[w_l];  // half-list lengths, low / high 16 bits
+      thr_l = cand_thr[w_l];
+      ok_l = ((c_l & 0xffff) <= kHalfCap && (c_l >> 16) <= kHalfCap) ? 1 : 0;  // else k_match_overflow's row
     }
     if (!ok_l) c_l = 0;
   }
@@ -1055,8 +1113,7 @@ __global__ void __launch_bounds__(256) k_match_rerank8(const float* __restrict__
     if (okr) v = *reinterpret_cast<const float4*>(desc + ((int64_t)ir * cap + rr) * 128 + k);
     *reinterpret_cast<float4*>(&sA[wv][r][k]) = v;
   }
-  // 2. list entries of the eight rows (contiguous), filtered and compacted in row order
-  const uint32_t* lists = cand + w0 * kCandCap;
+  // 2. list entries of the eight rows, filtered and compacted in row order
   int nk = 0;
 #pragma unroll 4
   for (int sidx = 0; sidx < kRrRows * kCandCap / 64; ++sidx) {
@@ -1065,8 +1122,9 @@ __global__ void __launch_bounds__(256) k_match_rerank8(const float* __restrict__
     const int cr = __shfl(c_l, r);
     const float tr = __shfl(thr_l, r);
     const int crh = pos < kHalfCap ? (cr & 0xffff) : (cr >> 16);
-    const bool valid = (pos & (kHalfCap - 1)) < crh && w0 + r < total;
-    const uint32_t ent = valid ? lists[e] : 0u;
+    const int64_t wr = __shfl(w_l, r);
+    const bool valid = (pos & (kHalfCap - 1)) < crh;  // crh = 0 for an idle item
+    const uint32_t ent = valid ? cand[wr * kCandCap + pos] : 0u;
     const bool keep = valid && __uint_as_float(ent & 0xffff0000u) <= tr;
     const uint64_t bal = __ballot(keep);
     if (pos == 0 && lane == (sidx * 64) % 64 && (e % kCandCap) == 0) sBeg[wv][r] = nk;  // row start
@@ -1118,7 +1176,7 @@ __global__ void __launch_bounds__(256) k_match_rerank8(const float* __restrict__
       const float nndr = d1 / d2;
       if (nndr <= ratio) { rb.col = j1; rb.nndr = nndr; }
     }
-    rows_out[w0 + lane] = rb;
+    rows_out[w_l] = rb;
   }
 }
 
@@ -1185,7 +1243,8 @@ void launch_match_mfma(const float* desc, const int32_t* count, int64_t cap, int
                        const _Float16* hi, const _Float16* lo, const float* norm2, const float* rnorm,
                        const void* pmax, const int32_t* pairs, int P, float ratio,
                        RowBest* rows, int max_rows, uint32_t* cand, int32_t* cand_n, float* cand_thr,
-                       int* ovf_count, int2* ovf_list, int32_t* units, hipStream_t st) {
+                       uint8_t* cand_skip, uint32_t* work_list, int* ovf_count, int2* ovf_list, int32_t* units,
+                       hipStream_t st) {
   // the half-CU form (STAGE 3) by default since round 5: 38.55k vs 37.91k img/s (six
   // interleaved runs each, one box; 38.51k vs 37.90k over four on another);
   // SFMFEAT_MATCH_STAGE=1 / reg: the one-workgroup-per-CU LDS-DMA / register-staged sweep (A/B)
@@ -1201,17 +1260,22 @@ void launch_match_mfma(const float* desc, const int32_t* count, int64_t cap, int
     const char* e = SFM_DIAG_ENV("SFMFEAT_MATCH_UNITS");
     return !(e && e[0] == '0');
   }();
+  int* const work_count = ovf_count + 1;  // beside the overflow counter (16 B)
   const int qbr = stage == 3 ? sweep_rows(3) : kQB;
   const int qb = (max_rows + qbr - 1) / qbr;
   const dim3 grid((unsigned)(8 * ((P + 7) / 8) * qb));
   if (!use_units) units = nullptr;
-  if (units) hipLaunchKernelGGL(k_match_units, dim3(1), dim3(1024), 0, st, count, pairs, P, max_rows, qbr, units);
+  // the re-rank's work list starts empty: k_match_units zeroes its length
+  if (units)
+    hipLaunchKernelGGL(k_match_units, dim3(1), dim3(1024), 0, st, count, pairs, P, max_rows, qbr, units, work_count);
+  else
+    (void)hipMemsetAsync(work_count, 0, sizeof(int), st);
   // ovf_count is zero here: set once at allocation, re-zeroed by k_match_compact
 #define SFM_SWEEP(A, ABL)                                                                             \
   hipLaunchKernelGGL((k_match_mfma<A, ABL>), grid, dim3(64 * sweep_waves(A)), 0, st, count, capP, hi, lo,  \
                      norm2, rnorm,                                                                         \
                      static_cast<const float2*>(pmax), pairs, P, max_rows, cand, cand_n, cand_thr, ovf_count, \
-                     ovf_list, units)
+                     ovf_list, units, ratio, cand_skip, rows, work_count, work_list)
   static const int abl = [] {  // timing ablations: diagnostic build only (SFM_ABLATION_ENV)
     const char* e = SFM_ABLATION_ENV("SFMFEAT_MATCH_ABL");
     return e ? atoi(e) : 0;
@@ -1246,13 +1310,16 @@ void launch_match_mfma(const float* desc, const int32_t* count, int64_t cap, int
   }();
   if (rr2 && P > rr8_max)
     hipLaunchKernelGGL(k_match_rerank2, dim3((unsigned)(((int64_t)P * max_rows + 7) / 8)), dim3(256), 0, st, desc,
-                       count, cap, pairs, P, ratio, max_rows, cand, cand_n, cand_thr, rows);
+                       count, cap, pairs, P, ratio, max_rows, cand, cand_n, cand_thr, work_count,
+                       work_list, rows);
   else if (P <= rr8_max)
     hipLaunchKernelGGL(k_match_rerank8, dim3((unsigned)(((int64_t)P * max_rows + 4 * kRrRows - 1) / (4 * kRrRows))),
-                       dim3(256), 0, st, desc, count, cap, pairs, P, ratio, max_rows, cand, cand_n, cand_thr, rows);
+                       dim3(256), 0, st, desc, count, cap, pairs, P, ratio, max_rows, cand, cand_n, cand_thr, work_count,
+                       work_list, rows);
   else
     hipLaunchKernelGGL(k_match_rerank, dim3((unsigned)(((int64_t)P * max_rows + 3) / 4)), dim3(256), 0, st, desc,
-                       count, cap, pairs, P, ratio, max_rows, cand, cand_n, cand_thr, rows);
+                       count, cap, pairs, P, ratio, max_rows, cand, cand_n, cand_thr, work_count,
+                       work_list, rows);
   // the overflow list's length stays on the device: a fixed grid strides over it
   hipLaunchKernelGGL(k_match_overflow, dim3(256), dim3(256), 0, st, desc, count, cap, pairs, ratio, rows, max_rows,
                      ovf_count, ovf_list);
