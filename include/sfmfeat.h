@@ -670,6 +670,32 @@ int32_t sfm_debug_geom(int32_t device, int32_t op, const double* in, int64_t n, 
 int32_t sfm_debug_nms(int32_t device, const float* R, int32_t B, int32_t H, int32_t W, int32_t ksize,
                       const uint32_t* tnms, int32_t tile, uint64_t* keys_out, int64_t* counts_out);
 
+/* The keypoint selection an extraction runs (NaiveSIFT.py:90-120), on host R planes instead of
+ * Harris's: per level the digit-1 histogram of the planes' order keys (host), the select scan,
+ * the certified NMS (not with force_exact) and then ONE selection launch over all the levels,
+ * on the null stream, with buffers sized as an extraction sizes them (kcap = max(k, 1); the
+ * levels' planes packed one after another, so a later level's planes need not be 16-B aligned).
+ *   R[l]           host [B][H[l]][W[l]] float32, l < nlevels (1 .. 4 levels)
+ *   x, y, conf     [nlevels][B][max(k, 1)] (slots past count[l][b] are 0), count [nlevels][B]
+ *   state          [nlevels][B][SFM_SELECT_STATE_WORDS] u32: the plane's final selection state -
+ *                  bucket[2], rank[2], odd, median (float bits; exact-path planes only), tnms,
+ *                  tcert, fallback (1: took the exact path, by the scan or at run time), tsub[2]
+ *   ncand          [nlevels][B] candidates of the certified NMS (0 with force_exact)
+ *   consts         [SFM_SELECT_CONSTS] the sizes the selection's branches turn on, for this k:
+ *                  keys sorted whole (sel_cap), its floor (kTopkDirect), confidence ties sorted in
+ *                  LDS (kTieLdsCap), keys selected in registers, median-list keys held in LDS
+ * consts is written before anything else is looked at except k; nlevels == 0 returns after that
+ * without a device call.  SFM_EINVAL: what a context rejects (k < 0 or above 8192, an even ksize,
+ * ksize / 2 > 15 when the certified NMS runs), B < 1, a level without pixels or of 2^26 and
+ * more, a negative half_window, vmin < 3 (an extraction passes max(65536, 128 k); below 3 the
+ * scan's ranks n - 3 vmin / 8 and n - vmin / 2 are not pixels), a null pointer. */
+#define SFM_SELECT_STATE_WORDS 11
+#define SFM_SELECT_CONSTS 5
+int32_t sfm_debug_select(int32_t device, int32_t nlevels, int32_t B, const float* const* R, const int32_t* H,
+                         const int32_t* W, const int32_t* half_window, int32_t k, int32_t ksize, int64_t vmin,
+                         int32_t force_exact, int32_t* x, int32_t* y, float* conf, int32_t* count,
+                         uint32_t* state, int64_t* ncand, int32_t* consts);
+
 /* Mean time (ms) of one fused Harris launch on synthetic planes, ablation variant abl
  * (0 full, 1 no digit histogram, 2 window sums over the first tap row only). */
 float sfm_debug_time_harris(int32_t device, int32_t abl, int32_t B, int32_t H, int32_t W,

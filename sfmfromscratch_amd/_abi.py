@@ -66,6 +66,23 @@ GEOM_DEBUG_SIGNATURES = {
 GEOM_ROW_IN = (3, 9, 6, 16, 18, 12, 64, 512)    # doubles per row, by op
 GEOM_ROW_OUT = (9, 3, 12, 4, 9, 3, 64, 512)
 SFM_GEOM_MAX_ROWS = 1 << 20
+# include/sfmfeat.h's probe of the keypoint selection on host R planes (tests/test_abi_cpu.py holds
+# it against the header's prototype): device, nlevels, B, R[], H[], W[], half_window[], k, ksize,
+# vmin, force_exact, x, y, conf, count, state, ncand, consts
+SELECT_DEBUG_SIGNATURES = {
+    "sfm_debug_select": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp,
+                                          ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
+                                          _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+SFM_SELECT_MAX_LEVELS = 4
+SFM_SELECT_MAX_K = 8192
+# the u32 words of a plane's selection state, in the library's order (median: float32 bits)
+SELECT_STATE_FIELDS = ("bucket0", "bucket1", "rank0", "rank1", "odd", "median", "tnms", "tcert", "fallback",
+                       "tsub0", "tsub1")
+SFM_SELECT_STATE_WORDS = len(SELECT_STATE_FIELDS)
+# the sizes the selection's branches turn on, in the order sfm_debug_select reports them
+SELECT_CONST_FIELDS = ("sel_cap", "topk_direct", "tie_lds_cap", "reg_keys", "med_cap")
+SFM_SELECT_CONSTS = len(SELECT_CONST_FIELDS)
 MATCH_CAND_CAP = 256   # list words per query row (two half-lists of 128)
 MATCH_PREP_ROWS = 16   # rows per block of the operands' (norm2, rnorm) maxima
 

@@ -109,6 +109,7 @@ SIGNATURES = {
     "sfm_debug_select_stats": (ctypes.c_int32, [_vp, _i32p, _i32p]),
     **_abi.MATCH_DEBUG_SIGNATURES,  # sfm_debug_match_operands, sfm_debug_match_windows, sfm_debug_match_skips
     **_abi.GEOM_DEBUG_SIGNATURES,  # sfm_debug_geom
+    **_abi.SELECT_DEBUG_SIGNATURES,  # sfm_debug_select
     "sfm_copy_wg": (ctypes.c_int32, [_vp, _vp, ctypes.c_int64, ctypes.c_int32, _vp]),
     "sfm_dist_unique_id": (ctypes.c_int32, [_u8p]),
     "sfm_dist_create": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _u8p, ctypes.POINTER(_vp)]),
@@ -607,6 +608,57 @@ def debug_geom(op: int, rows: np.ndarray, device: int = 0) -> np.ndarray:
     if n:
         check(load_library().sfm_debug_geom(device, op, rows.ctypes.data, n, out.ctypes.data))
     return out
+
+
+def select_constants(k: int) -> dict:
+    """The sizes the selection kernel's branches turn on at this k (_abi.SELECT_CONST_FIELDS), from
+    the library; no device call."""
+    consts = np.zeros(_abi.SFM_SELECT_CONSTS, np.int32)
+    check(load_library().sfm_debug_select(0, 0, 0, None, None, None, None, int(k), 1, 0, 0, None, None, None, None,
+                                          None, None, consts.ctypes.data))
+    return dict(zip(_abi.SELECT_CONST_FIELDS, consts.tolist()))
+
+
+def debug_select(levels, k: int, ksize: int, half_window, vmin: int, force_exact: bool = False, device: int = 0):
+    """sfm_debug_select: the selection sequence of an extraction on host R planes.  `levels`: one
+    float32 array [B, H_l, W_l] per level (or a single such array), `half_window` an int or one per
+    level.  -> (per level a dict of x, y [B, max(k, 1)] int32, conf float32, count [B], ncand [B]
+    and state: a dict of uint32 [B] per _abi.SELECT_STATE_FIELDS, median as float32), constants."""
+    if isinstance(levels, np.ndarray):
+        levels = [levels]
+    levels = [np.ascontiguousarray(R, dtype=np.float32) for R in levels]
+    nl = len(levels)
+    if not 1 <= nl <= _abi.SFM_SELECT_MAX_LEVELS or any(R.ndim != 3 for R in levels):
+        raise ValueError(f"debug_select: 1 to {_abi.SFM_SELECT_MAX_LEVELS} levels of [B, H, W] planes")
+    B = levels[0].shape[0]
+    if any(R.shape[0] != B for R in levels):
+        raise ValueError("debug_select: every level holds the same number of planes")
+    hw = [int(half_window)] * nl if np.isscalar(half_window) else [int(h) for h in half_window]
+    if len(hw) != nl:
+        raise ValueError("debug_select: one half_window per level")
+    k = int(k)
+    kcap = max(k, 1)
+    ptrs = (ctypes.c_void_p * nl)(*[R.ctypes.data for R in levels])
+    Hs = np.array([R.shape[1] for R in levels], np.int32)
+    Ws = np.array([R.shape[2] for R in levels], np.int32)
+    hws = np.array(hw, np.int32)
+    x = np.zeros((nl, B, kcap), np.int32)
+    y = np.zeros((nl, B, kcap), np.int32)
+    conf = np.zeros((nl, B, kcap), np.float32)
+    count = np.zeros((nl, B), np.int32)
+    state = np.zeros((nl, B, _abi.SFM_SELECT_STATE_WORDS), np.uint32)
+    ncand = np.zeros((nl, B), np.int64)
+    consts = np.zeros(_abi.SFM_SELECT_CONSTS, np.int32)
+    check(load_library().sfm_debug_select(device, nl, B, ctypes.addressof(ptrs), Hs.ctypes.data, Ws.ctypes.data,
+                                          hws.ctypes.data, k, int(ksize), int(vmin), int(bool(force_exact)),
+                                          x.ctypes.data, y.ctypes.data, conf.ctypes.data, count.ctypes.data,
+                                          state.ctypes.data, ncand.ctypes.data, consts.ctypes.data))
+    out = []
+    for l in range(nl):
+        st = {f: state[l, :, i].copy() for i, f in enumerate(_abi.SELECT_STATE_FIELDS)}
+        st["median"] = st["median"].view(np.float32)
+        out.append({"x": x[l], "y": y[l], "conf": conf[l], "count": count[l], "ncand": ncand[l], "state": st})
+    return out, dict(zip(_abi.SELECT_CONST_FIELDS, consts.tolist()))
 
 
 class Gate:

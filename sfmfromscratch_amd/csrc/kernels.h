@@ -446,6 +446,9 @@ struct SelectLevels {
   int n;
 };
 void launch_select_levels(const SelectLevels& g, int kcap, int k, int B, int ksize, hipStream_t st);
+// the sizes the selection's branches turn on at this k: keys sorted whole (sel_cap), its floor,
+// confidence ties sorted in LDS, keys selected in registers, median-list keys held in LDS
+void select_branch_sizes(int k, int32_t out[5]);
 
 // describe_q.hip: four keypoints per wavefront for window widths 2..22 (false: not handled)
 // out_count (the last level's launch): also write each slot's keypoint count

@@ -121,6 +121,9 @@ constexpr int kRegKeys = 8;  // keys per thread held in registers by the top-k (
 // fits on a CU beside one k_harris workgroup (78.8 KB).  Its VGPRs are kept at <= 88 for the
 // same reason: 4 waves per SIMD x 88 + one k_harris wave (160) = 512, the SIMD's register file
 // (tests/test_isa_guard_cpu.py pins both budgets).
+// u32 median-list keys that fit over the sel and tie areas
+__host__ __device__ constexpr int select_med_cap(int sel_cap) { return (sel_cap + kTieLdsCap) * 2; }
+
 struct SelectLds {
   uint64_t* sel;   // sel_cap
   uint64_t* tie;   // kTieLdsCap
@@ -571,7 +574,7 @@ __global__ void __launch_bounds__(1024) k_select(SelectLevels g, int kcap, int k
   L.scan = L.h + kHistBins;
   L.out = s_out;
   L.cnt = s_cnt;
-  L.med_cap = (sel_cap + kTieLdsCap) * 2;
+  L.med_cap = select_med_cap(sel_cap);
   L.sel_cap = sel_cap;
 
   const int tid = threadIdx.x;
@@ -625,6 +628,16 @@ static size_t select_lds_bytes(int sel_cap) {
 }
 
 size_t topk_lds_bytes() { return select_lds_bytes(select_sel_cap(kTopkLdsCap)); }
+
+// The sizes k_select's branches turn on at this k (sfm_debug_select hands them to the tests).
+void select_branch_sizes(int k, int32_t out[5]) {
+  const int sel_cap = select_sel_cap(k < 1 ? 1 : k);
+  out[0] = sel_cap;
+  out[1] = kTopkDirect;
+  out[2] = kTieLdsCap;
+  out[3] = kRegKeys * 1024;
+  out[4] = select_med_cap(sel_cap);
+}
 
 void launch_select_levels(const SelectLevels& g, int kcap, int k, int B, int ksize, hipStream_t st) {
   if (g.n < 1 || g.n > kSelectMaxLevels || B < 1) return;

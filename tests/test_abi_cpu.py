@@ -86,6 +86,49 @@ def test_abi_declares_the_geometry_probe_with_the_headers_signature():
         _native.debug_geom(8, np.zeros((1, 3)))
 
 
+def test_abi_declares_the_selection_probe_with_the_headers_signature():
+    res, args = header_prototype("sfm_debug_select")
+    assert _abi.SELECT_DEBUG_SIGNATURES["sfm_debug_select"] == (res, args)
+    assert _native.SIGNATURES["sfm_debug_select"] == (res, args)
+    text = open(HEADER).read()
+    assert re.search(rf"#define SFM_SELECT_STATE_WORDS {_abi.SFM_SELECT_STATE_WORDS}\b", text)
+    assert re.search(rf"#define SFM_SELECT_CONSTS {_abi.SFM_SELECT_CONSTS}\b", text)
+    # the constants come back without a device call, for every k a context accepts
+    c = _native.select_constants(1)
+    assert list(c) == list(_abi.SELECT_CONST_FIELDS) and all(v > 0 for v in c.values())
+    assert c["sel_cap"] == c["topk_direct"] and c["med_cap"] == 2 * (c["sel_cap"] + c["tie_lds_cap"])
+    assert _native.select_constants(0) == c
+    top = _native.select_constants(_abi.SFM_SELECT_MAX_K)
+    assert top["sel_cap"] == _abi.SFM_SELECT_MAX_K and top["med_cap"] == 2 * (top["sel_cap"] + top["tie_lds_cap"])
+    # argument errors come back before any device call
+    fn = _native.load_library().sfm_debug_select
+    R = np.zeros((1, 4, 4), np.float32)
+    ptr = (ctypes.c_void_p * 1)(R.ctypes.data)
+    null_level = (ctypes.c_void_p * 1)(None)
+    one = np.array([4], np.int32)
+    zero = np.zeros(1, np.int32)
+    o = np.zeros(64, np.int64)   # room for every output of one 4 x 4 plane at k <= 5
+    p, cp = o.ctypes.data, np.zeros(_abi.SFM_SELECT_CONSTS, np.int32).ctypes.data
+
+    def call(nlevels=1, B=1, R=ctypes.addressof(ptr), H=one.ctypes.data, W=one.ctypes.data, hw=zero.ctypes.data, k=5,
+             ksize=3, vmin=16, force_exact=0, x=p, consts=cp):
+        return fn(0, nlevels, B, R, H, W, hw, k, ksize, vmin, force_exact, x, p, p, p, p, p, consts)
+    bad = [dict(consts=None), dict(k=-1), dict(k=_abi.SFM_SELECT_MAX_K + 1), dict(nlevels=-1),
+           dict(nlevels=_abi.SFM_SELECT_MAX_LEVELS + 1), dict(B=0), dict(R=None), dict(H=None), dict(W=None),
+           dict(hw=None), dict(x=None), dict(ksize=0), dict(ksize=4), dict(ksize=33), dict(vmin=2),
+           dict(H=zero.ctypes.data), dict(hw=np.array([-1], np.int32).ctypes.data),
+           dict(R=ctypes.addressof(null_level))]
+    for kw in bad:
+        assert call(**kw) == _abi.SFM_EINVAL, kw
+    assert call(nlevels=0, R=None, H=None, W=None, hw=None, x=None) == _abi.SFM_OK
+    # the binding's own checks
+    for levels in ([], [R] * 5, [R, np.zeros((2, 4, 4), np.float32)], [np.zeros((4, 4), np.float32)]):
+        with pytest.raises(ValueError):
+            _native.debug_select(levels, 5, 3, 0, 16)
+    with pytest.raises(ValueError):
+        _native.debug_select([R, R], 5, 3, [0], 16)
+
+
 def test_struct_layout_matches_header(tmp_path):
     """ctypes mirror == the C compiler's layout of sfm_params (offsets and size)."""
     import subprocess

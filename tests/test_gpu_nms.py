@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from sfmfromscratch_amd import _native
+from tests.select_ref import planes, ring_planes
 
 pytestmark = pytest.mark.gpu
 
@@ -39,17 +40,6 @@ def numpy_candidates(R: np.ndarray, tnms: int, ksize: int) -> np.ndarray:
     return np.sort(keys)
 
 
-def planes(B, H, W, seed):
-    rng = np.random.default_rng(seed)
-    R = rng.standard_normal((B, H, W)).astype(np.float32)
-    R[0] = np.round(R[0] * 2) / 2           # plateaus: many equal neighbours
-    if B > 1:
-        R[1] = np.abs(R[1]) * 1e3           # positive, large
-    if B > 2:
-        R[2, :, : W // 2] = 0.0             # a flat half (R == 0 plateaus)
-    return R
-
-
 @pytest.mark.parametrize("B,H,W", [(3, 37, 100), (2, 64, 256), (3, 270, 480), (2, 9, 4), (1, 540, 960),
                                    (2, 33, 102)])
 @pytest.mark.parametrize("quantile", [0.0, 0.5, 0.97])
@@ -62,25 +52,6 @@ def test_certified_nms_stream_and_tile_vs_numpy(B, H, W, quantile):
         for b in range(B):
             assert got[b].size == want[b].size, (tile, b, got[b].size, want[b].size)
             assert np.array_equal(got[b], want[b]), (tile, b)
-
-
-def ring_planes(H, W, kh):
-    """Planes on which the outermost row and column of the window decide: over a flat -1
-    background (below the threshold 0), sites of one pixel A (value 1 + site) and one larger
-    pixel B (100 + site) at offset r x (sy, sx) from it, for the eight directions and r = kh
-    (B is on the window's border: A is suppressed) and r = kh + 1 (just outside: A stays).
-    Sites sit 2 kh + 3 columns apart, so no site's pixels lie in another's windows.  A random
-    plane almost never notices a window one row or column short at ksize 31; this one must."""
-    offs = [(sy * r, sx * r) for r in (kh, kh + 1)
-            for sy, sx in ((-1, -1), (-1, 0), (-1, 1), (0, -1), (0, 1), (1, -1), (1, 0), (1, 1))]
-    per, ay = W // (2 * kh + 3), H // 2
-    assert per >= 1 and ay - (kh + 1) >= 0 and ay + kh + 1 < H
-    out = np.full((-(-len(offs) // per), H, W), -1.0, np.float32)
-    for s, (dy, dx) in enumerate(offs):
-        ax = kh + 1 + (s % per) * (2 * kh + 3)
-        out[s // per, ay, ax] = 1.0 + s
-        out[s // per, ay + dy, ax + dx] = 100.0 + s
-    return out
 
 
 @pytest.mark.parametrize("ksize", [1, 5, 7, 9, 11, 13, 21, 31])

@@ -38,6 +38,9 @@ def test_harris_R_median_bitexact_vs_oracle(H, W, pp):
     Ro = O.harris_response(img, pp)
     assert np.array_equal(bits(R), bits(Ro))
     assert np.float32(med) == O.median(Ro)
+    # ... and the median extraction computes (k_select's exact path; debug_harris runs the stand-alone kernels)
+    sel, _ = _native.debug_select(R[None], 10, p.ksize, 0, 65536, force_exact=True)
+    assert bits(sel[0]["state"]["median"])[0] == bits(O.median(Ro))[0]
     _, _, _, dbg = O.detect(img, 10 ** 7, 0, pp, debug=True)
     assert ncand == dbg["n_candidates"]
 
