@@ -468,7 +468,12 @@ int32_t sfm_triangulate_tracks_dev(sfm_ctx* ctx, const int32_t* track_offsets, c
                                    int32_t nimg, int64_t cap, const double* P, const uint8_t* cam_valid,
                                    int32_t n_cam, double* X, int32_t* out_views, void* stream);
 
-/* sfm_ingest_rgb for B frames: rgb [B][H][W][3] uint8 -> gray [B][H2][W2] float32. */
+/* sfm_ingest_rgb for B frames: rgb [B][H][W][3] uint8 -> gray [B][H2][W2] float32 (device
+ * pointers).  Enqueued on `stream`, not synchronised.  The tap tables and the temp image belong
+ * to the context: one ingest call at a time per context, on one stream.  A call whose shape
+ * (H, W, H2, W2) differs from the context's last one, or whose temp is larger, first waits for
+ * the work already enqueued on `stream` and uploads its tables there; a call on another stream
+ * needs the caller to have synchronised the previous one. */
 int32_t sfm_ingest_rgb_dev(sfm_ctx* ctx, const uint8_t* rgb, int32_t B, int32_t H, int32_t W,
                            int32_t H2, int32_t W2, float* gray, void* stream);
 

@@ -15,19 +15,23 @@ int ingest_impl(sfm_ctx* c, const uint8_t* rgb, int B, int H, int W, int H2, int
   int rc;
   IngestWs& g = c->ingest;
   const bool newh = g.w != W || g.w2 != W2, newv = g.h != H || g.h2 != H2;
+  const size_t tmp_bytes = (size_t)B * H * W2 * 3 + 16;
+  // The tables and the temp are the context's, and the previous call's kernels may still read
+  // them on `st` (the call is not synchronised): a new shape, or a larger temp, first waits for
+  // that work, then uploads on `st` itself.  A blocking hipMemcpy would be ordered against the
+  // null stream only, which a non-blocking stream such as torch's side streams never joins.
+  if (newh || newv || g.tmp.bytes < tmp_bytes) HIPCHK(c, hipStreamSynchronize(st));
   if (newh) {
+    g.w = g.w2 = -1;
     g.ksh = build_resample_table(W, W2, g.th);
     if ((rc = ensure(c, g.tab_h, g.th.size() * 4))) return rc;
-    HIPCHK(c, hipMemcpy(g.tab_h.p, g.th.data(), g.th.size() * 4, hipMemcpyHostToDevice));
-    g.w = W;
-    g.w2 = W2;
+    HIPCHK(c, hipMemcpyAsync(g.tab_h.p, g.th.data(), g.th.size() * 4, hipMemcpyHostToDevice, st));
   }
   if (newv) {
+    g.h = g.h2 = -1;
     g.ksv = build_resample_table(H, H2, g.tv);
     if ((rc = ensure(c, g.tab_v, g.tv.size() * 4))) return rc;
-    HIPCHK(c, hipMemcpy(g.tab_v.p, g.tv.data(), g.tv.size() * 4, hipMemcpyHostToDevice));
-    g.h = H;
-    g.h2 = H2;
+    HIPCHK(c, hipMemcpyAsync(g.tab_v.p, g.tv.data(), g.tv.size() * 4, hipMemcpyHostToDevice, st));
   }
   if (newh || newv) {
     std::vector<int32_t> cm, sets;
@@ -36,12 +40,14 @@ int ingest_impl(sfm_ctx* c, const uint8_t* rgb, int B, int H, int W, int H2, int
     if (g.rows) {
       if ((rc = ensure(c, g.colmap, cm.size() * 4))) return rc;
       if ((rc = ensure(c, g.sets, sets.size() * 4))) return rc;
-      HIPCHK(c, hipMemcpy(g.colmap.p, cm.data(), cm.size() * 4, hipMemcpyHostToDevice));
-      HIPCHK(c, hipMemcpy(g.sets.p, sets.data(), sets.size() * 4, hipMemcpyHostToDevice));
+      HIPCHK(c, hipMemcpyAsync(g.colmap.p, cm.data(), cm.size() * 4, hipMemcpyHostToDevice, st));
+      HIPCHK(c, hipMemcpyAsync(g.sets.p, sets.data(), sets.size() * 4, hipMemcpyHostToDevice, st));
       g.nsets = (int)(sets.size() / ks);
     }
+    HIPCHK(c, hipStreamSynchronize(st));  // cm and sets are locals; as PnpWs's sample stream
+    g.w = W, g.w2 = W2, g.h = H, g.h2 = H2;  // only now: a failed upload is redone by the next call
   }
-  if ((rc = ensure(c, g.tmp, (size_t)B * H * W2 * 3 + 16))) return rc;
+  if ((rc = ensure(c, g.tmp, tmp_bytes))) return rc;
   launch_ingest_rgb(rgb, as<uint8_t>(g.tmp), gray, as<int32_t>(g.tab_h), g.ksh, as<int32_t>(g.tab_v), g.ksv,
                     g.rows ? as<int32_t>(g.colmap) : nullptr, as<int32_t>(g.sets), g.nsets, B, H, W, H2, W2, st);
   HIPCHK(c, hipGetLastError());
