@@ -779,6 +779,17 @@ int32_t sfm_debug_pose_candidates(sfm_ctx* ctx, int32_t* cand_idx, int64_t entri
  * must be that call's P * iters (else SFM_ESTATE; a single-pair host call with n < 8 runs
  * nothing and counts as 0 entries); SFM_EINVAL for a null pointer or entries < 0. */
 int32_t sfm_debug_ransac_fits(sfm_ctx* ctx, double* F, int32_t* counts, int64_t entries);
+/* The per-sample fits of the last sfm_pnp_ransac_dev call on this context and the start pose of
+ * the last PnP call's refinement (host outputs; synchronises the device): hyp [iters][12], each
+ * sample's hypothesis (R row-major, then t) as the count and selection kernels read it, all 12
+ * NaN for a degenerate sample; counts [iters], its inlier count (0 for a NaN hypothesis);
+ * start_Rt [12], the pose the refinement started from: the winning hypothesis (NaN without a
+ * pose) or, after sfm_pnp_dev, the DLT's pose over all points.  A copy of the workspaces;
+ * nothing is recomputed.  entries must be that call's iters, or 0 when it ran no sample (n < 6,
+ * iters == 0) and after sfm_pnp_dev: then only start_Rt is written and hyp, counts may be null.
+ * SFM_EINVAL with a message for any other entries, when the context has made no PnP call (or
+ * its last one failed), for a null start_Rt, or for null hyp or counts with entries > 0. */
+int32_t sfm_debug_pnp_fits(sfm_ctx* ctx, double* hyp, int32_t* counts, double* start_Rt, int64_t entries);
 /* Level l's R maps (what 0) or level images (what 1) of the last extraction -> out [B][h][w]
  * (device, on `stream`; diagnostics). */
 int32_t sfm_debug_copy_level(sfm_ctx* ctx, int32_t l, int32_t what, float* out, void* stream);

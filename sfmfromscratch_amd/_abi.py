@@ -74,6 +74,11 @@ SELECT_DEBUG_SIGNATURES = {
                                           ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
                                           _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
+# include/sfmfeat.h's read-back of the PnP samples (host pointers as void*; tests/test_abi_cpu.py
+# holds it against the header's prototype): ctx, hyp, counts, start_Rt, entries
+PNP_DEBUG_SIGNATURES = {
+    "sfm_debug_pnp_fits": (ctypes.c_int32, [_vp, _vp, _vp, _vp, ctypes.c_int64]),
+}
 SFM_SELECT_MAX_LEVELS = 4
 SFM_SELECT_MAX_K = 8192
 # the u32 words of a plane's selection state, in the library's order (median: float32 bits)

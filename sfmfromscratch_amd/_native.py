@@ -110,6 +110,7 @@ SIGNATURES = {
     **_abi.MATCH_DEBUG_SIGNATURES,  # sfm_debug_match_operands, sfm_debug_match_windows, sfm_debug_match_skips
     **_abi.GEOM_DEBUG_SIGNATURES,  # sfm_debug_geom
     **_abi.SELECT_DEBUG_SIGNATURES,  # sfm_debug_select
+    **_abi.PNP_DEBUG_SIGNATURES,  # sfm_debug_pnp_fits
     "sfm_copy_wg": (ctypes.c_int32, [_vp, _vp, ctypes.c_int64, ctypes.c_int32, _vp]),
     "sfm_dist_unique_id": (ctypes.c_int32, [_u8p]),
     "sfm_dist_create": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _u8p, ctypes.POINTER(_vp)]),
@@ -393,6 +394,17 @@ class Context:
         check(self.lib.sfm_debug_ransac_fits(self.handle, F.ctypes.data_as(_dp), counts.ctypes.data_as(_i32p),
                                              P * iters), self.handle)
         return F, counts
+
+    def pnp_fits(self, iters: int):
+        """(hyp [iters, 12] float64: R row-major then t, counts [iters] int32, start_Rt [12]) of the last
+        PnP call; iters 0 after sfm_pnp_dev or a call that ran no sample (only start_Rt is defined)."""
+        hyp = np.empty((iters, 12), np.float64)
+        counts = np.empty(iters, np.int32)
+        start = np.empty(12, np.float64)
+        check(self.lib.sfm_debug_pnp_fits(self.handle, hyp.ctypes.data if iters else None,
+                                          counts.ctypes.data if iters else None, start.ctypes.data, iters),
+              self.handle)
+        return hyp, counts, start
 
     # -------- device-pointer API (throughput path; pointers are ints) --------
     def ingest_rgb_dev(self, rgb_ptr: int, B: int, H: int, W: int, H2: int, W2: int, gray_ptr: int,

@@ -63,17 +63,20 @@ int32_t sfm_pnp_ransac_dev(sfm_ctx* c, const double* X, const double* x, const d
   if ((rc = ensure(c, w.idx, 16))) return rc;
   if ((rc = ensure(c, w.hyp, (size_t)std::max(iters, 1) * 12 * 8))) return rc;
   if ((rc = ensure(c, w.Rt, 12 * 8))) return rc;
-  int32_t* counts = out_counts;
-  if (!counts) {
-    if ((rc = ensure(c, w.counts, (size_t)std::max(iters, 1) * 4))) return rc;
-    counts = as<int32_t>(w.counts);
-  } else if (!sampled && iters > 0) {
+  // the kernels count into the caller's table when there is one; the workspace's gets a copy
+  // below (sfm_debug_pnp_fits reads the workspace: the caller's table may be gone by then)
+  if ((rc = ensure(c, w.counts, (size_t)std::max(iters, 1) * 4))) return rc;
+  int32_t* counts = out_counts ? out_counts : as<int32_t>(w.counts);
+  if (out_counts && !sampled && iters > 0)
     HIPCHK(c, hipMemsetAsync(out_counts, 0, (size_t)iters * 4, st));  // n < 6: no sample counts anything
-  }
+  w.last_entries = -1;
   launch_pnp_ransac(X, x, K, n, as<int32_t>(w.idx), w.idx_stride, iters, threshold, max_refine_iter,
                     as<double>(w.hyp), counts, as<double>(w.Rt), out_inliers, out_n, out_iter, R, t, out_status,
                     out_cost, st);
   HIPCHK(c, hipGetLastError());
+  if (out_counts && sampled)
+    HIPCHK(c, hipMemcpyAsync(w.counts.p, out_counts, (size_t)iters * 4, hipMemcpyDeviceToDevice, st));
+  w.last_entries = sampled ? iters : 0;
   return SFM_OK;
 }
 
@@ -91,8 +94,26 @@ int32_t sfm_pnp_dev(sfm_ctx* c, const double* X, const double* x, const double* 
   HIPCHK(c, hipSetDevice(c->device));
   int rc;
   if ((rc = ensure(c, c->pnp.Rt, 12 * 8))) return rc;
+  c->pnp.last_entries = -1;
   launch_pnp(X, x, K, n, max_refine_iter, as<double>(c->pnp.Rt), R, t, out_status, out_cost, (hipStream_t)stream);
   HIPCHK(c, hipGetLastError());
+  c->pnp.last_entries = 0;
+  return SFM_OK;
+}
+
+int32_t sfm_debug_pnp_fits(sfm_ctx* c, double* hyp, int32_t* counts, double* start_Rt, int64_t entries) {
+  if (!c) return SFM_EINVAL;
+  if (!start_Rt || entries < 0 || (entries > 0 && (!hyp || !counts)))
+    return set_err(c, SFM_EINVAL, "sfm_debug_pnp_fits: a null pointer or entries < 0");
+  if (c->pnp.last_entries < 0) return set_err(c, SFM_EINVAL, "sfm_debug_pnp_fits: no PnP call on this context");
+  if (entries != c->pnp.last_entries)
+    return set_err(c, SFM_EINVAL, "sfm_debug_pnp_fits: not the last PnP call's samples");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipDeviceSynchronize());  // the call ran on the caller's stream
+  HIPCHK(c, hipMemcpy(start_Rt, c->pnp.Rt.p, 12 * 8, hipMemcpyDeviceToHost));
+  if (entries == 0) return SFM_OK;
+  HIPCHK(c, hipMemcpy(hyp, c->pnp.hyp.p, (size_t)entries * 12 * 8, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(counts, c->pnp.counts.p, (size_t)entries * 4, hipMemcpyDeviceToHost));
   return SFM_OK;
 }
 

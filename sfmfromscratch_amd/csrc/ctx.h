@@ -185,6 +185,9 @@ struct RegistryWs {
 struct PnpWs {
   DevBuf idx, hyp, counts, Rt;
   int idx_n = -1, idx_iters = -1, idx_stride = 0;
+  // sfm_debug_pnp_fits: -1 before the first call, the samples that ran in the last
+  // sfm_pnp_ransac_dev (its iters; 0 when n < 6), 0 after sfm_pnp_dev
+  int64_t last_entries = -1;
 };
 
 // Bundle adjustment (sfm_bundle_adjust_dev): everything kernels.h BaProblem points at between

@@ -10,6 +10,10 @@ same pivot order); `route="svd"` takes numpy's SVD instead, for the admission ch
 tests/test_pnp_cpu.py.  The sample stream is numpy's own (np.random.seed(5);
 np.random.choice(n, 6, replace=False) per iteration).
 
+The second half is apart from all that: rule 2 and the all-points DLT in 60 digits (mpmath;
+`hypotheses_mp`, `dlt_all_mp`), the admission of a sample by the reference's own conditioning
+figures, the degenerate scenes, and the arrays of tests/golden/pnp_fits.npz.
+
 Only tests/ and tools/gen_golden_pnp.py, tools/bench_pnp.py import this module."""
 from __future__ import annotations
 
@@ -60,16 +64,19 @@ def sample_systems(Xs, xs):
     return A[:, :11], s, c
 
 
-def null_elimination(A):
+def null_elimination(A, last=False):
     """A [S, 11, 12] -> p [S, 12] with p[11] = 1 (NaN rows where a pivot is zero): Gaussian
-    elimination with partial pivoting, the first row of the largest magnitude."""
+    elimination with partial pivoting, the first row of the largest magnitude.  last=True takes
+    the last such row instead: not the rule, but what tests/test_pnp_fits_cpu.py holds against
+    it to show that the `lattice` scene can tell the two apart."""
     A = A.copy()
     S = len(A)
     ar = np.arange(S)
     ok = np.ones(S, bool)
     with np.errstate(all="ignore"):
         for c in range(11):
-            piv = c + np.argmax(np.abs(A[:, c:, c]), axis=1)
+            col = np.abs(A[:, c:, c])
+            piv = c + (col.shape[1] - 1 - np.argmax(col[:, ::-1], axis=1) if last else np.argmax(col, axis=1))
             rc, rp = A[ar, c].copy(), A[ar, piv].copy()
             A[ar, c], A[ar, piv] = rp, rc
             d = A[:, c, c]
@@ -123,8 +130,18 @@ def hypotheses(X, x, K, idx, route="elim"):
     """One (R, t) per row of idx [S, 6]."""
     xn = normalised_pixels(x, K)
     A, s, c = sample_systems(X[idx], xn[idx])
-    p = null_elimination(A) if route == "elim" else null_svd(A)
+    p = null_svd(A) if route == "svd" else null_elimination(A, last=route == "elim_last")
     return pose_from_p(p, s, c)
+
+
+def elimination_cond_m(X, x, K, idx, last=False):
+    """cond M [S] of the elimination route's projection matrices (inf where a pivot is zero)."""
+    A, s, c = sample_systems(X[idx], normalised_pixels(x, K)[idx])
+    p = null_elimination(A, last)
+    M = np.where(np.isfinite(p).all(axis=1)[:, None, None], p.reshape(-1, 3, 4)[:, :, :3], np.zeros((3, 3)))
+    sv = np.linalg.svd(M, compute_uv=False)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(sv[:, 2] > 0, sv[:, 0] / sv[:, 2], np.inf)
 
 
 def errors(X, x, K, R, t):
@@ -364,3 +381,308 @@ NO_POSE = ["n5", "it0"]
 # cases whose winner must hold every planted inlier: all but a single sample (its winner is
 # that sample, whatever it is worth) and the all-random correspondences
 HOLDS = [k for k in ransac_cases() if k not in NO_POSE + ["it1", "random"]]
+
+
+# ---------------- the rule in 60 digits (mpmath), apart from the elimination route ----------------
+# Only tools/gen_golden_pnp.py and the CPU tests call these; the GPU tests read their results
+# from tests/golden/pnp_fits.npz and never import mpmath.
+
+MP_DIGITS = 60
+S_MAX = 1e4        # a sample is admitted when sigma_1 / sigma_11 of its 11 x 12 system <= S_MAX
+CONDM_MAX = 1e3    # ... and cond M of its projection matrix's left 3 x 3 block <= CONDM_MAX
+DLT_GAP_MIN = 10.0  # the all-points DLT is admitted when sigma_11 / sigma_12 >= DLT_GAP_MIN
+MAX_LEFT_OUT = 0.05  # share of a case's samples that may fall outside the admission
+MAX_IN_BAND = 1e-4   # share of (sample, point) tests that may stay undecided
+BIG = 1e300        # what an infinite conditioning figure is stored as
+
+
+def _mp_inputs(X, x, K):
+    from mpmath import mp
+    mp.dps = MP_DIGITS
+    f = mp.mpf
+    Kx = [[f(float(K[r, c])) for c in range(3)] for r in range(3)]
+    Xm = [[f(float(v)) for v in row] for row in X]
+    xn = []
+    for u, v in x:
+        q2 = 1 / Kx[2][2]
+        q1 = (f(float(v)) - Kx[1][2] * q2) / Kx[1][1]
+        q0 = (f(float(u)) - Kx[0][1] * q1 - Kx[0][2] * q2) / Kx[0][0]
+        xn.append((q0 / q2, q1 / q2))
+    return Xm, xn
+
+
+def _mp_system(Xm, xn, rows, drop_last):
+    """The DLT system of the points `rows` (Hartley-normalised among themselves) -> (A, s, c);
+    drop_last leaves out the last point's second row (the 11 x 12 system of a sample)."""
+    from mpmath import mp
+    m = len(rows)
+    c = [mp.fsum(Xm[j][k] for j in rows) / m for k in range(3)]
+    d = [[Xm[j][k] - c[k] for k in range(3)] for j in rows]
+    md = mp.fsum(mp.sqrt(mp.fsum(v * v for v in r)) for r in d) / m
+    if md == 0:
+        return None, None, c
+    s = mp.sqrt(3) / md
+    A = mp.zeros(2 * m - (1 if drop_last else 0), 12)
+    for i, j in enumerate(rows):
+        Yh = [s * d[i][0], s * d[i][1], s * d[i][2], mp.mpf(1)]
+        u, v = xn[j]
+        for k in range(4):
+            A[2 * i, k] = Yh[k]
+            A[2 * i, 8 + k] = -u * Yh[k]
+            if not (drop_last and i == m - 1):
+                A[2 * i + 1, 4 + k] = Yh[k]
+                A[2 * i + 1, 8 + k] = -v * Yh[k]
+    return A, s, c
+
+
+def _mp_null(A):
+    """The right singular vector of A's smallest singular value and all 12 singular values
+    (descending; an 11-row system's twelfth is 0): the eigen-decomposition of A^T A, which in 60
+    digits is that vector for every system admitted below (sigma_1 / sigma_11 <= 1e4 costs 8 of
+    the 60 digits)."""
+    from mpmath import mp
+    E, Q = mp.eigsy(A.T * A)
+    order = sorted(range(12), key=lambda k: E[k])
+    sv = [mp.sqrt(max(E[k], 0)) for k in reversed(order)]
+    return [Q[k, order[0]] for k in range(12)], sv
+
+
+def _mp_pose(p, s, c):
+    """P -> (R, t, cond M): the sign from det M, R = M (M^T M)^(-1/2), sigma the mean singular
+    value of M, t = (P[:, 3] / sigma - s R c) / s.  None where M is singular."""
+    from mpmath import mp
+    M = mp.matrix(3, 3)
+    for r in range(3):
+        for k in range(3):
+            M[r, k] = p[4 * r + k]
+    p4 = [p[3], p[7], p[11]]
+    if mp.det(M) < 0:
+        M, p4 = -M, [-v for v in p4]
+    w, V = mp.eigsy(M.T * M)
+    if min(w) <= 0:
+        return None
+    q = [mp.sqrt(v) for v in w]
+    B = V * mp.diag([1 / v for v in q]) * V.T
+    R = M * B
+    sigma = mp.fsum(q) / 3
+    t = [(p4[r] / sigma - s * mp.fsum(R[r, k] * c[k] for k in range(3))) / s for r in range(3)]
+    return R, t, max(q) / min(q)
+
+
+def _mp_fit(Xm, xn, rows, drop_last):
+    """-> (Rt [12] float64 (NaN without a pose), conditioning of the system, cond M); the
+    conditioning is sigma_1 / sigma_11 of a sample's system, sigma_11 / sigma_12 of a full one."""
+    from mpmath import mp
+    nan = np.full(12, np.nan)
+    A, s, c = _mp_system(Xm, xn, rows, drop_last)
+    if A is None:
+        return nan, BIG, BIG
+    p, sv = _mp_null(A)
+    if drop_last:
+        fig = float(sv[0] / sv[10]) if sv[10] > mp.mpf(10) ** -50 * sv[0] else BIG
+    else:
+        fig = float(sv[10] / sv[11]) if sv[11] > 0 else BIG
+    pose = _mp_pose(p, s, c)
+    if pose is None:
+        return nan, min(fig, BIG), BIG
+    R, t, cm = pose
+    Rt = np.array([float(R[r, k]) for r in range(3) for k in range(3)] + [float(v) for v in t])
+    return Rt, min(fig, BIG), min(float(cm), BIG)
+
+
+def hypotheses_mp(X, x, K, idx, cache=None):
+    """Rule 2 of DESIGN.md §13D from the float64 inputs in 60 digits, one row of idx [S, 6] at a
+    time -> (R [S, 3, 3], t [S, 3], sigma_1 / sigma_11 [S], cond M [S]).  cache: a dict shared
+    between calls on the same (X, x, K)."""
+    Xm, xn = _mp_inputs(np.asarray(X, np.float64), np.asarray(x, np.float64), np.asarray(K, np.float64))
+    cache = {} if cache is None else cache
+    S = len(idx)
+    Rt, s111, cm = np.zeros((S, 12)), np.zeros(S), np.zeros(S)
+    for k, row in enumerate(idx):
+        key = tuple(int(v) for v in row)
+        if key not in cache:
+            cache[key] = _mp_fit(Xm, xn, list(key), True)
+        Rt[k], s111[k], cm[k] = cache[key]
+    return Rt[:, :9].reshape(S, 3, 3), Rt[:, 9:], s111, cm
+
+
+def dlt_all_mp(X, x, K):
+    """The all-points DLT in 60 digits -> (R [3, 3], t [3], sigma_11 / sigma_12)."""
+    Xm, xn = _mp_inputs(np.asarray(X, np.float64), np.asarray(x, np.float64), np.asarray(K, np.float64))
+    Rt, gap, _ = _mp_fit(Xm, xn, list(range(len(Xm))), False)
+    return Rt[:9].reshape(3, 3), Rt[9:], gap
+
+
+def admitted(s111, condM):
+    return (s111 <= S_MAX) & (condM <= CONDM_MAX)
+
+
+def dlt_all_svd(X, x, K):
+    """`dlt_all` with the null vector from an SVD of A itself (the second float64 route)."""
+    X, x, K = np.asarray(X, np.float64), np.asarray(x, np.float64), np.asarray(K, np.float64)
+    xn = normalised_pixels(x, K)
+    c = X.mean(axis=0)
+    d = X - c
+    s = np.sqrt(3.0) / np.sqrt((d * d).sum(axis=1)).mean()
+    Yh = np.column_stack([s * d, np.ones(len(X))])
+    A = np.zeros((2 * len(X), 12))
+    A[0::2, 0:4], A[0::2, 8:12] = Yh, -xn[:, 0:1] * Yh
+    A[1::2, 4:8], A[1::2, 8:12] = Yh, -xn[:, 1:2] * Yh
+    R, t = pose_from_p(np.linalg.svd(A)[2][-1][None], np.array([s]), c[None])
+    return R[0], t[0]
+
+
+def pose_deviation(R, t, Rr, tr):
+    """max |dR| [S] and |dt| / max(1, |t_ref|) [S]."""
+    dR = np.abs(R - Rr).reshape(len(R), -1).max(axis=1)
+    dt = np.linalg.norm(t - tr, axis=1) / np.maximum(1.0, np.linalg.norm(tr, axis=1))
+    return dR, dt
+
+
+def rotation_defect(R):
+    """max |R R^T - I| [S] (NaN rows give NaN)."""
+    with np.errstate(invalid="ignore"):
+        return np.abs(R @ np.swapaxes(R, 1, 2) - np.eye(3)).reshape(len(R), -1).max(axis=1)
+
+
+# ---------------- degenerate and near-degenerate scenes ----------------
+
+DEG_N, DEG_ITERS = 60, 50
+
+
+def _seen(X, K, rng, noise=0.6):
+    R, t = rot(0.12, -0.05, 0.03), np.array([-1.0, 0.05, 0.1])
+    q = (X @ R.T + t) @ K.T
+    return np.round(q[:, :2] / q[:, 2:] + rng.normal(0, noise, (len(X), 2)))
+
+
+def degenerate_cases():
+    """name -> (X, x, K, iterations): world points for which rule 2's 11 x 12 systems lose rank
+    exactly (plane, ident, dup), nearly (tilted, slab3, collinear), here and there (lattice) or
+    not at all (slab1)."""
+    out = {}
+    K = K_SCENE
+    rng = np.random.default_rng(300)
+    # the exact plane z = 8, coordinates on a 1/4 grid: the centred z are exactly 0, so three
+    # columns of every sample's system are exactly 0
+    X = np.column_stack((rng.integers(-12, 13, DEG_N) / 4.0, rng.integers(-8, 9, DEG_N) / 4.0, np.full(DEG_N, 8.0)))
+    out["plane"] = (X, _seen(X, K, rng), K, DEG_ITERS)
+    # the same plane tilted and rounded to float32: nothing is exactly 0 any more
+    Xt = (X @ rot(0.3, 0.2, 0.1).T + np.array([0.2, -0.1, 1.0])).astype(np.float32).astype(np.float64)
+    out["tilted"] = (Xt, _seen(Xt, K, rng), K, DEG_ITERS)
+    for name, half in (("slab3", 1e-3), ("slab1", 0.1)):
+        Xs = np.column_stack((rng.uniform(-3, 3, DEG_N), rng.uniform(-2, 2, DEG_N), 8.0 + rng.uniform(-half, half, DEG_N)))
+        Xs = Xs.astype(np.float32).astype(np.float64)
+        out[name] = (Xs, _seen(Xs, K, rng), K, DEG_ITERS)
+    # every correspondence twice: a sample that draws both copies has two identical pairs of rows
+    # (seed 301: three samples share the largest count, 60 of 60)
+    rd = np.random.default_rng(301)
+    Xd = rd.uniform([-3, -2, 4], [3, 2, 12], (DEG_N // 2, 3)).astype(np.float32).astype(np.float64)
+    xd = _seen(Xd, K, rd)
+    out["dup"] = (np.repeat(Xd, 2, axis=0), np.repeat(xd, 2, axis=0), K, DEG_ITERS)
+    # points of one line
+    lam = rng.permutation(np.arange(-30, 30))[:DEG_N] / 8.0
+    Xl = (np.array([0.3, -0.2, 8.0]) + lam[:, None] * np.array([0.6, 0.3, 0.5])).astype(np.float32).astype(np.float64)
+    out["collinear"] = (Xl, _seen(Xl, K, rng), K, DEG_ITERS)
+    # an integer lattice (z in steps of 1/8): many samples hold two rows of equal magnitude in a
+    # pivot column and a coplanar or collinear subset, so which of the equal rows is taken decides
+    # the bits, and for one sample whether a pivot is exactly 0
+    rl = np.random.default_rng(310)
+    Xg = np.column_stack((rl.integers(-3, 4, DEG_N).astype(np.float64), rl.integers(-2, 3, DEG_N).astype(np.float64),
+                          8.0 + rl.integers(-2, 3, DEG_N) / 8.0))
+    out["lattice"] = (Xg, _seen(Xg, K, rl), K, DEG_ITERS)
+    # six identical points: the mean distance to the centroid is 0
+    Xi = np.tile(np.array([[0.5, -0.25, 8.0]]), (6, 1))
+    out["ident"] = (Xi, _seen(Xi, K, rng, noise=0.0), K, 9)
+    return out
+
+
+DEG_REFERENCED = ["slab1", "dup"]   # the degenerate-scene cases whose 60-digit hypotheses the fixture holds
+
+
+def dlt_cases():
+    """name -> (X, x, K) for the all-points DLT: n = 6, 7, one wave and one point more, the edges
+    of the 256-thread reduction, and the skewed K.  Every point is planted: with the outliers of
+    n64, n65 and skew the system has no null vector to speak of (sigma_11 / sigma_12 below 2.2)."""
+    c = ransac_cases()
+    out = {k: (c[k][0], c[k][1], c[k][5]) for k in ("n6", "n7")}
+    out["dlt64"] = scene(100, 64)[:2] + (K_SCENE,)
+    out["dlt65"] = scene(101, 65)[:2] + (K_SCENE,)
+    out.update({k: (c[k][0], c[k][1], c[k][5]) for k in LM_CASES[1:]})
+    out["dltskew"] = scene(100, 40, K=K_SKEW)[:2] + (K_SKEW,)
+    return out
+
+
+DLT_CASES_N = [k for k in dlt_cases() if k != "dltskew"]   # the sizes; dltskew is the skewed K
+
+
+def fits_cases():
+    """name -> (X, x, K, iterations) of every case with a 60-digit reference per sample: the
+    fixture cases of pnp.npz that run samples, and DEG_REFERENCED."""
+    out = {k: (v[0], v[1], v[5], v[6]) for k, v in ransac_cases().items() if len(v[0]) >= 6 and v[6] > 0}
+    deg = degenerate_cases()
+    out.update({k: deg[k] for k in DEG_REFERENCED})
+    return out
+
+
+# The largest deviation of the two float64 routes of this module (the elimination restatement,
+# LAPACK's SVD; for the all-points DLT eigh of A^T A and the SVD of A) from the 60-digit
+# reference over the admitted samples of every case, measured by tests/test_pnp_cpu.py, which
+# holds these constants to the measurement (they may not be below it, nor above twice it).
+# 100 x the constant, capped at 1e-8, bounds the device (tests/test_gpu_pnp_fits.py).
+CPU_MEASURED_R, CPU_MEASURED_T = 5e-11, 3.5e-11            # measured 4.001e-11 (n65, SVD), 2.852e-11 (n63)
+CPU_MEASURED_DLT_R, CPU_MEASURED_DLT_T = 5.5e-13, 4.5e-12  # measured 4.400e-13, 3.458e-12 (n6, eigh of A^T A)
+FIT_CAP = 1e-8
+
+
+def fit_bounds():
+    return {"bound_R": min(FIT_CAP, 100 * CPU_MEASURED_R), "bound_t": min(FIT_CAP, 100 * CPU_MEASURED_T),
+            "bound_dlt_R": min(FIT_CAP, 100 * CPU_MEASURED_DLT_R), "bound_dlt_t": min(FIT_CAP, 100 * CPU_MEASURED_DLT_T)}
+
+
+def fixture_arrays(progress=None):
+    """Every array of tests/golden/pnp_fits.npz, in the file's order.  Needs mpmath."""
+    out = {}
+    caches = {}
+    for name, (X, x, K, iters) in fits_cases().items():
+        # (it1, it50 and it300 are one scene and prefixes of one stream)
+        cache = caches.setdefault((X.tobytes(), x.tobytes(), K.tobytes()), {})
+        R, t, s111, cm = hypotheses_mp(X, x, K, samples(len(X), iters), cache)
+        out[f"{name}_R"], out[f"{name}_t"] = R, t
+        f32 = lambda a: np.minimum(a, 3e38).astype(np.float32)   # (the figures are for reading; the flag decides)
+        out[f"{name}_s111"], out[f"{name}_condM"] = f32(s111), f32(cm)
+        out[f"{name}_admitted"] = admitted(s111, cm)
+        if progress:
+            a = out[f"{name}_admitted"]
+            progress(f"{name}: {iters} samples, {int((~a).sum())} left out, worst admitted s1/s11 "
+                     f"{s111[a].max():.3e} cond M {cm[a].max():.3e}")
+    for name, (X, x, K, iters) in degenerate_cases().items():
+        out[f"{name}_X"], out[f"{name}_x"], out[f"{name}_K"], out[f"{name}_iters"] = X, x, K, np.int32(iters)
+    for name, (X, x, K) in dlt_cases().items():
+        if name.startswith("dlt"):
+            out[f"{name}_X"], out[f"{name}_x"], out[f"{name}_K"] = X, x, K
+        R, t, gap = dlt_all_mp(X, x, K)
+        out[f"{name}_dlt_R"], out[f"{name}_dlt_t"], out[f"{name}_dlt_gap"] = R, t, np.float64(gap)
+        if progress:
+            progress(f"dlt {name}: n {len(X)} sigma11/sigma12 {gap:.3e}")
+    out["fits"] = np.array(list(fits_cases()))
+    out["degenerate"] = np.array(list(degenerate_cases()))
+    out["dlt"] = np.array(list(dlt_cases()))
+    for k, v in fit_bounds().items():
+        out[k] = np.float64(v)
+    return out
+
+
+def fixture_bytes(arrays):
+    """The .npz container with a constant member timestamp: equal arrays give equal bytes."""
+    import io
+    import zipfile
+    buf = io.BytesIO()
+    with zipfile.ZipFile(buf, "w", compression=zipfile.ZIP_DEFLATED, compresslevel=9) as zf:
+        for key, val in arrays.items():
+            info = zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            with zf.open(info, "w", force_zip64=False) as fid:
+                np.lib.format.write_array(fid, np.asanyarray(val), allow_pickle=False)
+    return buf.getvalue()

@@ -57,6 +57,18 @@ def test_abi_declares_the_matcher_read_backs_with_the_headers_signatures(name):
     assert fn(*[None if a is ctypes.c_void_p else 0 for a in args]) == _abi.SFM_EINVAL
 
 
+def test_abi_declares_the_pnp_read_back_with_the_headers_signature():
+    res, args = header_prototype("sfm_debug_pnp_fits")
+    assert _abi.PNP_DEBUG_SIGNATURES["sfm_debug_pnp_fits"] == (res, args)
+    assert _native.SIGNATURES["sfm_debug_pnp_fits"] == (res, args)
+    lib = _native.load_library()
+    # without a context the call returns before any device call
+    assert lib.sfm_debug_pnp_fits(None, None, None, None, 0) == _abi.SFM_EINVAL
+    buf = np.zeros(12)
+    assert lib.sfm_debug_pnp_fits(None, buf.ctypes.data, None, buf.ctypes.data, 0) == _abi.SFM_EINVAL
+    assert lib.sfm_abi_version() == 1
+
+
 def test_abi_declares_the_geometry_probe_with_the_headers_signature():
     res, args = header_prototype("sfm_debug_geom")
     assert _abi.GEOM_DEBUG_SIGNATURES["sfm_debug_geom"] == (res, args)

@@ -6,7 +6,14 @@ the marginal-comparison flags) and scipy's least_squares(method="lm", xtol = fto
 over all points) with its own scipy minimum.  Nothing here comes from OpenCV or from the
 reference project: the fixture holds data of this repository's restatement and of scipy only.
 
-usage: python tools/gen_golden_pnp.py [--check]   (--check: compare with the committed file)"""
+With --fits: tests/golden/pnp_fits.npz instead — rule 2 of DESIGN.md §13D in 60 digits (mpmath,
+tests/pnp_ref.py hypotheses_mp / dlt_all_mp): the (R, t) of every sample of every sampled case,
+its conditioning figures and admission flag, the all-points DLT's pose at the reduction edges,
+the inputs of the degenerate scenes, and the device bounds that follow from the float64
+routes' own deviation (tests/pnp_ref.py fit_bounds).  The arithmetic is mpmath's and the
+container has constant timestamps: the same bytes every run.
+
+usage: python tools/gen_golden_pnp.py [--fits] [--check]   (--check: compare with the committed file)"""
 import argparse
 import os
 import sys
@@ -19,6 +26,7 @@ sys.path.insert(0, ROOT)
 from tests import pnp_ref as PR  # noqa: E402
 
 OUT = os.path.join(ROOT, "tests", "golden", "pnp.npz")
+OUT_FITS = os.path.join(ROOT, "tests", "golden", "pnp_fits.npz")
 REFINE_KEYS = ("R", "t", "cost0", "cost", "iters", "lm_iters", "status", "firm", "all_firm")
 
 
@@ -59,7 +67,18 @@ def build():
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--check", action="store_true")
+    ap.add_argument("--fits", action="store_true")
     args = ap.parse_args()
+    if args.fits:
+        data = PR.fixture_bytes(PR.fixture_arrays(progress=lambda line: print(line, flush=True)))
+        if args.check:
+            same = open(OUT_FITS, "rb").read() == data
+            print("pnp_fits.npz:", "the same bytes" if same else "differs")
+            sys.exit(0 if same else 1)
+        with open(OUT_FITS, "wb") as f:
+            f.write(data)
+        print(f"wrote {OUT_FITS}: {len(data)} bytes")
+        return
     out = build()
     if args.check:
         z = np.load(OUT, allow_pickle=False)
