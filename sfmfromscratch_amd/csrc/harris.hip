@@ -42,11 +42,6 @@ constexpr int kHT = 64;   // output tile columns (rows: HarrisShape::TH, 64 or 3
 // levels with at most this many 64 x 64 tiles per resident workgroup take the 64 x 32 form
 // (SFMFEAT_HARRIS_SMALL overrides; 0 = never)
 constexpr int kHarrisSmallTiles = 4;
-// 1: the 7 x 7 window's default form keeps product planes in LDS (form 3; SFMFEAT_HARRIS_PP)
-constexpr int kHarrisProductPlanes = 0;
-// 1: the 7 x 7 window's large levels sum their windows on MFMA (form 4; SFMFEAT_HARRIS_MF,
-// 2 = every level)
-constexpr int kHarrisMfma = 0;
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 // the window's tap pairs, read through the constant address space: wave-uniform scalar loads
@@ -112,66 +107,24 @@ constexpr int kStampSlots = 48;
 __device__ uint64_t* g_harris_stamps;
 __device__ int64_t g_harris_stamps_cap;  // u64 slots behind g_harris_stamps (workgroups beyond it skip)
 
-// NPAIR: output row pairs per thread.  2: 256 threads x (4 columns x 4 rows), 2 waves per
-// SIMD at up to 256 VGPRs.  1: 512 threads x (4 columns x 2 rows), 4 waves per SIMD at up to
-// 128 VGPRs (the window's packed fmas issue faster at 4 waves per SIMD, DESIGN_LOG.md §B), at
-// the price of each gradient row's products being formed by twice as many threads.
-// F (the workgroup form):
-//   0: 256 threads x (4 columns x 4 rows), 64 x 64 tiles, 2 workgroups per CU (2 waves per
-//      SIMD at up to 256 VGPRs) — the default;
-//   1: 512 threads x (4 x 2), 64 x 64 tiles, 2 per CU (4 waves per SIMD at 128 VGPRs);
-//   2: 256 threads x (4 x 2), 64 x 32 tiles, 3 per CU (3 waves per SIMD at 168 VGPRs): the
-//      small levels, whose 64 x 64 tiles would give each resident workgroup only a few
-//      tiles to walk one after another;
-//   3: as 0, but the Sobel phase forms the three products once per pixel and LDS holds
-//      product planes Ix^2, Iy^2, IxIy (the image tile aliased into them) instead of the two
-//      gradient planes, so the window phase reads products instead of re-forming them for
-//      every row it feeds (each gradient row's products were formed by 2.5 threads).
-//   4: the window sums on the matrix pipe (v_mfma_f32_4x4x1_16b_f32, see "MFMA window"
-//      below): 256 threads, 64 x 64 tiles, 2 workgroups per CU; wave w owns tile columns
-//      16w .. 16w+15 and lane l tile row l.
-//   5: as 0, with S_xy on the matrix pipe beside the VALU's S_xx and S_yy: the lanes of each
-//      4-lane MFMA block share their 4 columns and hold 4 different row groups (rq from lane
-//      bits 0-1 and 5, tq from bits 2-4), so an MFMA accumulator per output row o puts
-//      pixel (4rq + o, 4tq + i) in register i of the thread that owns it in form 0, and the
-//      B operand is the IxIy product that thread already formed for its VALU work.
+// F (the workgroup form), 256 threads each:
+//   0: 4 columns x 4 rows per thread (two output row pairs), 64 x 64 tiles, 2 workgroups per
+//      CU (2 waves per SIMD at up to 256 VGPRs) — the default;
+//   2: 4 columns x 2 rows per thread (one row pair), 64 x 32 tiles, 3 workgroups per CU (3
+//      waves per SIMD at 168 VGPRs): the small levels, whose 64 x 64 tiles would give each
+//      resident workgroup only a few tiles to walk one after another.
+// F keeps the values 0 and 2: the kernels' mangled names are looked up by
+// tests/test_isa_guard_cpu.py and tools/isa_phases.py.  (The forms measured slower — 512
+// threads, product planes in LDS, window sums or S_xy on MFMA — are in DESIGN_LOG.md §V.)
 template <int F>
 struct HarrisShape {
-  static constexpr bool PP = F == 3;                     // product planes in LDS
-  static constexpr bool MF = F == 4;                     // window sums on MFMA
-  static constexpr bool HY = F == 5;                     // S_xy on MFMA, S_xx / S_yy on VALU
-  static constexpr int NPAIR = (F == 0 || F == 3 || F == 4 || F == 5) ? 2 : 1;  // output row pairs per thread
-  static constexpr int NT = F == 1 ? 512 : 256;          // threads per workgroup
+  static_assert(F == 0 || F == 2, "harris workgroup form");
+  static constexpr int NPAIR = F == 0 ? 2 : 1;           // output row pairs per thread
+  static constexpr int NT = 256;                         // threads per workgroup
   static constexpr int RPT = 2 * NPAIR;                  // output rows per thread
   static constexpr int TH = RPT * 4 * (NT / 64);         // tile rows (tile columns: kHT)
   static constexpr int WPC = F == 2 ? 3 : 2;             // workgroups per CU
   static constexpr int WPE = WPC * NT / 256;             // waves per SIMD
-};
-
-// MFMA window (form 4).  v_mfma_f32_4x4x1_16b_f32 is 16 independent 4 x 4 outer products
-// per instruction, D[lane 4b+j][reg i] += A[lane 4b+i] * B[lane 4b+j], and its result is
-// bitwise a k-ordered fmaf chain (tools/mfma_f32_probe.hip, profiles/r04_mfma_f32_probe.txt:
-// 0 of 256 results differ over chains of 1 .. 4096 steps).  A horizontal window row is a
-// banded (Toeplitz) product: for a 4-column strip at tile columns x .. x+3, step s = 0 ..
-// KS+2 takes gradient column x + s (B: the product at that column in the lane's row) and the
-// tap g[dy][s - i] for output column x + i (A: 0 outside the band).  Each output pixel then
-// sees its taps in row-major order with zero taps in between, and fmaf(0, p, acc) == acc
-// for finite p and acc != -0 (acc starts at +0 and a sum of finite values never rounds to
-// -0), so the chain is the reference's.  7 of every 10 MACs are taps at KS = 7.
-template <int KS>
-struct MfWin {
-  static constexpr int NS = KS + 3;              // steps per tap row (4 columns + KS - 1)
-  static constexpr int NC = 12 + NS;             // gradient columns a wave reads per row (4 strips)
-  static constexpr int NB4 = (NC + 3) / 4;       // b128 LDS reads per row per plane
-  // row stride: >= the tile's gradient columns and the last wave's reads, stride/4 odd
-  // (ds_read_b128 lane groups of 16 rows then hit 16 distinct 16-B slots)
-  static constexpr int stride() {
-    int s = kHT + KS - 1;
-    if (s < 48 + 4 * NB4) s = 48 + 4 * NB4;
-    s = (s + 3) / 4 * 4;
-    if (((s / 4) & 1) == 0) s += 4;
-    return s;
-  }
 };
 
 // The VALU window's schedule: a thread's window sums are a sequence of blocks, one per
@@ -218,10 +171,6 @@ template <int KS, bool VEC, int ABL = 0, int F = 0>
 __global__ void __launch_bounds__(HarrisShape<F>::NT, HarrisShape<F>::WPE) k_harris(HarrisLevels lvs, const float* __restrict__ gk, float alpha) {
   constexpr int NT = HarrisShape<F>::NT, RPT = HarrisShape<F>::RPT, NPAIR = HarrisShape<F>::NPAIR;
   constexpr int TH = HarrisShape<F>::TH;
-  constexpr bool PP = HarrisShape<F>::PP;
-  constexpr bool MF = HarrisShape<F>::MF;
-  constexpr bool HY = HarrisShape<F>::HY;
-  static_assert(!MF || (TH == 64 && NT == 256), "MFMA form: 4 waves x 64 rows");
   // this workgroup's level (one launch may hold several pyramid levels: the small levels'
   // tiles share a launch instead of each paying a launch and a tail)
   int li = 0;
@@ -240,11 +189,9 @@ __global__ void __launch_bounds__(HarrisShape<F>::NT, HarrisShape<F>::WPE) k_har
   // a 16-lane group of a ds_read_b128 holds 8 column groups x 2 row groups (RPT rows apart):
   // RPT * stride / 4 == 8 (mod 16) 16-B chunks keeps the chunks 8*rq + tq (mod 16) distinct,
   // i.e. stride == 8 (mod 32) floats for RPT 4 and == 16 (mod 32) for RPT 2
-  constexpr int PWP = MF ? MfWin<KS>::stride()
-                    : HY ? ((kHT + KS - 1 <= 76 && 60 + NVP <= 76) ? 76 : ((60 + NVP <= 108) ? 108 : 140))
-                    : RPT == 4 ? ((kHT + KS - 1 <= 72 && 60 + NVP <= 72) ? 72 : ((60 + NVP <= 104) ? 104 : 136))
+  constexpr int PWP = RPT == 4 ? ((kHT + KS - 1 <= 72 && 60 + NVP <= 72) ? 72 : ((60 + NVP <= 104) ? 104 : 136))
                                : ((kHT + KS - 1 <= 80 && 60 + NVP <= 80) ? 80 : ((60 + NVP <= 112) ? 112 : 144));
-  static_assert(PWP >= kHT + KS - 1 && (MF || 60 + NVP <= PWP), "harris LDS row stride");
+  static_assert(PWP >= kHT + KS - 1 && 60 + NVP <= PWP, "harris LDS row stride");
   constexpr int NS = PWP / 4;               // 4-wide gradient strips per row
   constexpr int XA = (GA + 1 + 3) / 4 * 4;  // image tile margin left of the output tile
   constexpr int SH = XA - GA - 1;           // image column of gradient column 0, minus 1
@@ -254,20 +201,17 @@ __global__ void __launch_bounds__(HarrisShape<F>::NT, HarrisShape<F>::WPE) k_har
   constexpr int IW4 = IWP / 4;
   constexpr int NIMG = VEC ? (IH * IW4 + NT - 1) / NT : (IH * IWP + NT - 1) / NT;
   static_assert(NIMG <= 64, "prefetch mask");
-  // gradient planes (or, PP, product planes) and the image tile; PP aliases the image tile
-  // into the product planes (the tile is dead once the Sobel pass has read it)
-  constexpr int NPL = PP ? 3 : 2;
-  static_assert(!PP || IH * IWP <= NPL * PH * PWP, "image tile alias");
-  __shared__ __attribute__((aligned(16))) float s_pl[NPL * PH * PWP + (PP ? 0 : IH * IWP)];
+  // the two gradient planes Ix, Iy, then the image tile
+  __shared__ __attribute__((aligned(16))) float s_pl[2 * PH * PWP + IH * IWP];
   float (*const s_g)[PH][PWP] = reinterpret_cast<float (*)[PH][PWP]>(s_pl);
-  float (*const s_img)[IWP] = reinterpret_cast<float (*)[IWP]>(s_pl + (PP ? 0 : NPL * PH * PWP));
+  float (*const s_img)[IWP] = reinterpret_cast<float (*)[IWP]>(s_pl + 2 * PH * PWP);
   // digit-1 histogram, flushed once per workgroup: two copies (even / odd lanes) where the LDS
   // budget of WPC workgroups per CU allows, halving the same-address serialisation of one
   // wave's LDS adds; the second copy is shifted by 16 words, half of the 32 banks a ds_add_u32
   // lane group spans, so a bucket's two copies never share a bank (round 6: a 32-word shift
   // put them on the same bank; L0 alone 397 -> 390 us, profiles/r06_harris_hist_variants.txt)
   constexpr int kHistCopy = kMedBins1 + 16;
-  constexpr int kLdsRest = 4 * (NPL * PH * PWP + (PP ? 0 : IH * IWP)) + 1024;
+  constexpr int kLdsRest = 4 * (2 * PH * PWP + IH * IWP) + 1024;
   constexpr int NHC = kLdsRest + 8 * kHistCopy <= 163840 / HarrisShape<F>::WPC ? 2 : 1;
   __shared__ uint32_t s_hist[NHC * kHistCopy];
   __shared__ uint32_t s_last, s_red[10];
@@ -295,25 +239,9 @@ __global__ void __launch_bounds__(HarrisShape<F>::NT, HarrisShape<F>::WPE) k_har
   for (int i = tid; i < NHC * kHistCopy; i += NT) s_hist[i] = 0u;
   const int lane = tid & 63, wv = tid >> 6;
   uint32_t* const s_hc = s_hist + (NHC == 2 ? (lane & 1) * kHistCopy : 0);
-  // MFMA window: the banded tap operand A(dy, s), lane 4b+i: g[dy][s - i] (0 off the band).
-  // Every block of an A operand holds the same taps, so the instruction's A broadcast
-  // (cbsz 4: block abid's A to all 16 blocks; tools/mfma_f32_probe.hip) lets one VGPR carry
-  // 16 steps: step k = dy * NS + s sits in block k % 16 of tapV[k / 16]
-  constexpr int MNS = (MF || HY) ? MfWin<KS>::NS : 1;
-  constexpr int NTAPV = (MF || HY) ? (KS * MNS + 15) / 16 : 1;
-  float tapV[NTAPV];
-  if constexpr (MF || HY) {
-#pragma unroll
-    for (int v = 0; v < NTAPV; ++v) {
-      const int k = 16 * v + (lane >> 2), dy = k / MNS, t = k % MNS - (lane & 3);
-      const bool on = k < KS * MNS && t >= 0 && t < KS;
-      tapV[v] = on ? gk[on ? dy * KS + t : 0] : 0.0f;
-    }
-  }
-  // columns 4tq .. 4tq+3, rows RPT*rq .. RPT*rq+RPT-1 (HY: a 4-lane block shares tq)
-  const int tq = HY ? (((lane >> 2) & 7) | ((wv & 1) << 3)) : ((lane & 7) | ((wv & 1) << 3));
-  const int rq = HY ? ((lane & 3) | (((lane >> 5) & 1) << 2) | ((wv >> 1) << 3))
-                    : (((lane >> 3) & 7) | ((wv >> 1) << 3));
+  // columns 4tq .. 4tq+3, rows RPT*rq .. RPT*rq+RPT-1
+  const int tq = (lane & 7) | ((wv & 1) << 3);
+  const int rq = ((lane >> 3) & 7) | ((wv >> 1) << 3);
 
   // image tile of `tile` -> registers (zero outside the image = BORDER_CONSTANT)
   typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -425,22 +353,16 @@ __global__ void __launch_bounds__(HarrisShape<F>::NT, HarrisShape<F>::WPE) k_har
       }
     }
     if constexpr (ABL != 4) __syncthreads();
-    // (PP: after the product pass, so the prefetch registers are not live beside the
-    // strips' gradients)
-    if (!PP && tile + nwg < ntiles) prefetch(tile + nwg);
+    if (tile + nwg < ntiles) prefetch(tile + nwg);
     // 1. gradients (NaiveSIFT.py:201-213: fma chain over the non-zero Sobel taps in
     //    row-major order from +0; k*p is exact for these taps) for 4-wide strips; outside
     //    the image the gradients are 0, so their products (:61-63) are the zero border of
     //    the window sums (:67-69)
     //    Packed over column pairs (q, q+1) when the strip's image reads are pair-aligned
     //    (each half an IEEE fma, as the scalar chain); interior tiles skip the masking.
-    constexpr int NSI = (PH * NS + NT - 1) / NT;  // strips per thread (PP: held in registers)
-    float4 GXs[PP ? NSI : 1], GYs[PP ? NSI : 1];
     auto sobel = [&](auto maskedc) {
       constexpr bool MASKED = decltype(maskedc)::value;
-#pragma unroll
-      for (int it = 0; it < (PP ? NSI : 1); ++it)
-      for (int sidx = tid + it * NT; sidx < PH * NS; sidx += (PP ? PH * NS : NT)) {
+      for (int sidx = tid; sidx < PH * NS; sidx += NT) {
         const int py = sidx / NS, px0 = (sidx - py * NS) * 4;
         f32x2 w[3][2 * NR4];
 #pragma unroll
@@ -515,13 +437,8 @@ __global__ void __launch_bounds__(HarrisShape<F>::NT, HarrisShape<F>::WPE) k_har
             gyq[q] = inside ? gyq[q] : 0.0f;
           }
         }
-        if constexpr (PP) {
-          GXs[it] = make_float4(gxq[0], gxq[1], gxq[2], gxq[3]);
-          GYs[it] = make_float4(gyq[0], gyq[1], gyq[2], gyq[3]);
-        } else {
-          *reinterpret_cast<float4*>(&s_g[0][py][px0]) = make_float4(gxq[0], gxq[1], gxq[2], gxq[3]);
-          *reinterpret_cast<float4*>(&s_g[1][py][px0]) = make_float4(gyq[0], gyq[1], gyq[2], gyq[3]);
-        }
+        *reinterpret_cast<float4*>(&s_g[0][py][px0]) = make_float4(gxq[0], gxq[1], gxq[2], gxq[3]);
+        *reinterpret_cast<float4*>(&s_g[1][py][px0]) = make_float4(gyq[0], gyq[1], gyq[2], gyq[3]);
       }
     };
     // every gradient position of the tile (incl. the unused stride padding) in the image
@@ -529,10 +446,8 @@ __global__ void __launch_bounds__(HarrisShape<F>::NT, HarrisShape<F>::WPE) k_har
     if (grad_in) sobel(std::false_type{});
     else sobel(std::true_type{});
     // the first window block's taps do not depend on LDS: their loads fly across the barrier
-    if constexpr (!MF) {
-      load_taps(std::integral_constant<int, 0>{});
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    load_taps(std::integral_constant<int, 0>{});
+    __builtin_amdgcn_sched_barrier(0);
     if constexpr (ABL != 4) __syncthreads();
     if constexpr (F == 0) {
       // fused pyramid: the tile's 8 x 8 blocks of this level -> the next three exact 2x levels
@@ -561,106 +476,7 @@ __global__ void __launch_bounds__(HarrisShape<F>::NT, HarrisShape<F>::WPE) k_har
         }
       }
     }
-    if constexpr (PP) {
-      // the image tile is dead: the three products of every gradient (NaiveSIFT.py:61-63, the
-      // same IEEE products the window phase formed) into their planes
-#pragma unroll
-      for (int it = 0; it < NSI; ++it) {
-        const int sidx = tid + it * NT;
-        if (sidx < PH * NS) {
-          const int py = sidx / NS, px0 = (sidx - py * NS) * 4;
-          const f32x2 x0 = {GXs[it].x, GXs[it].y}, x1 = {GXs[it].z, GXs[it].w};
-          const f32x2 y0 = {GYs[it].x, GYs[it].y}, y1 = {GYs[it].z, GYs[it].w};
-          const f32x2 a0 = x0 * x0, a1 = x1 * x1, b0 = y0 * y0, b1 = y1 * y1, c0 = x0 * y0, c1 = x1 * y1;
-          *reinterpret_cast<float4*>(&s_g[0][py][px0]) = make_float4(a0.x, a0.y, a1.x, a1.y);
-          *reinterpret_cast<float4*>(&s_g[1][py][px0]) = make_float4(b0.x, b0.y, b1.x, b1.y);
-          *reinterpret_cast<float4*>(&s_g[2][py][px0]) = make_float4(c0.x, c0.y, c1.x, c1.y);
-        }
-      }
-      __syncthreads();
-      if (tile + nwg < ntiles) prefetch(tile + nwg);
-    }
 
-    if constexpr (MF) {
-      // 2'. window sums on the matrix pipe (see MfWin): lane l = tile row l, wave w = tile
-      //     columns 16w .. 16w+15 as 4 strips q of 4 columns; acc[q][pl][i] = column
-      //     16w + 4q + i.  Per tap row dy the lane reads its gradient row l + dy (columns
-      //     16w .. 16w + NC - 1), forms the three products of each column once (the same IEEE
-      //     products as :61-63) and feeds every strip whose band covers that column.
-      using MW = MfWin<KS>;
-      typedef float f32x4 __attribute__((ext_vector_type(4)));
-      f32x4 macc[4][3];
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int pl = 0; pl < 3; ++pl) macc[q][pl] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-      // gradient rows are read one tap row ahead (two register buffers)
-      float X[2][4 * MW::NB4], Y[2][4 * MW::NB4];
-      auto load_row = [&](int dy, float (&x)[4 * MW::NB4], float (&y)[4 * MW::NB4]) {
-        const float4* rx = reinterpret_cast<const float4*>(&s_g[0][lane + dy][16 * wv]);
-        const float4* ry = reinterpret_cast<const float4*>(&s_g[1][lane + dy][16 * wv]);
-#pragma unroll
-        for (int c4 = 0; c4 < MW::NB4; ++c4) {
-          const float4 a = rx[c4], c = ry[c4];
-          x[4 * c4] = a.x, x[4 * c4 + 1] = a.y, x[4 * c4 + 2] = a.z, x[4 * c4 + 3] = a.w;
-          y[4 * c4] = c.x, y[4 * c4 + 1] = c.y, y[4 * c4 + 2] = c.z, y[4 * c4 + 3] = c.w;
-        }
-      };
-      load_row(0, X[0], Y[0]);
-      constexpr int NDY = (ABL == 2) ? 1 : KS;
-      static_for<NDY>([&](auto dyc) {
-        constexpr int dy = decltype(dyc)::value, cb = dy & 1;
-        if constexpr (dy + 1 < NDY) load_row(dy + 1, X[cb ^ 1], Y[cb ^ 1]);
-        // the row's products, once per column
-        float pxx[MW::NC], pyy[MW::NC], pxy[MW::NC];
-#pragma unroll
-        for (int c = 0; c < MW::NC; ++c) {
-          const float xv = X[cb][c], yv = Y[cb][c];
-          pxx[c] = xv * xv, pyy[c] = yv * yv, pxy[c] = xv * yv;
-        }
-        // step-major: every step feeds all 12 accumulators (4 strips x 3 planes), so an
-        // accumulator's next MFMA is 12 instructions behind its last
-        static_for<MW::NS>([&](auto sc) {
-          constexpr int s = decltype(sc)::value, k = dy * MW::NS + s;
-          const float tv = tapV[k / 16];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            macc[q][0] = __builtin_amdgcn_mfma_f32_4x4x1f32(tv, pxx[4 * q + s], macc[q][0], 4, k % 16, 0);
-            macc[q][1] = __builtin_amdgcn_mfma_f32_4x4x1f32(tv, pyy[4 * q + s], macc[q][1], 4, k % 16, 0);
-            macc[q][2] = __builtin_amdgcn_mfma_f32_4x4x1f32(tv, pxy[4 * q + s], macc[q][2], 4, k % 16, 0);
-          }
-        });
-      });
-      // 3'. R (:71-74) per pixel, the digit-1 histogram, R stored as 16-B row segments
-      const int gy = ty0 + lane;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int gx0 = tx0 + 16 * wv + 4 * q;
-        float Rq[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float sxx = macc[q][0][i], syy = macc[q][1][i], sxy = macc[q][2][i];
-          const float t1v = sxx * syy;
-          const float t2v = sxy * sxy;
-          const float det = t1v - t2v;
-          const float tr = sxx + syy;
-          const float tr2 = tr * tr;
-          const float at = alpha * tr2;
-          Rq[i] = det - at;
-          if (ABL != 1) atomicAdd(&s_hc[fkey(Rq[i]) >> (32 - kMedBits1)], (gy < H && gx0 + i < W) ? 1u : 0u);
-        }
-        if (gy < H) {
-          float* dst = Rp + (int64_t)gy * W + gx0;
-          if (VEC) {
-            if (gx0 < W) *reinterpret_cast<float4*>(dst) = make_float4(Rq[0], Rq[1], Rq[2], Rq[3]);
-          } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-              if (gx0 + i < W) dst[i] = Rq[i];
-          }
-        }
-      }
-    } else {
     // 2. window sums (:67-69): per pixel an fma chain over the KS x KS taps in row-major
     //    order.  acc[p][pl][q] = (row 4rq+2p, row 4rq+2p+1) at column 4tq+q; gradient row
     //    4rq+r feeds tap row r-2p of the pair's first row and r-2p-1 of its second: packed
@@ -672,11 +488,6 @@ __global__ void __launch_bounds__(HarrisShape<F>::NT, HarrisShape<F>::WPE) k_har
       for (int pl = 0; pl < 3; ++pl)
 #pragma unroll
         for (int q = 0; q < 4; ++q) acc[p][pl][q] = f32x2{0.0f, 0.0f};
-    // HY: S_xy of output row RPT*rq + o in MFMA accumulator o (register i = column 4tq + i)
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
-    f32x4 macc2[HY ? 4 : 1];
-#pragma unroll
-    for (int o = 0; o < (HY ? 4 : 1); ++o) macc2[o] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     // The loads are software-pipelined by one block (WinBlocks) and their places are pinned
     // with sched_barrier: lgkmcnt counts scalar loads and LDS reads together and scalar loads
     // return out of order, so any wait on a tap is lgkmcnt(0) and drains whatever was issued
@@ -684,44 +495,25 @@ __global__ void __launch_bounds__(HarrisShape<F>::NT, HarrisShape<F>::WPE) k_har
     // issued at the start of the block before (its taps, its row's gradients), then issues the
     // next block's loads, then runs its fmas behind them.
     f32x2 P[3][NP2];                               // the current row's products
-    f32x2 X[PP ? 1 : NVP / 2], Y[PP ? 1 : NVP / 2];  // the next row's gradients
-    f32x2 Pn[PP ? 3 : 1][PP ? NP2 : 1];            // PP: the next row's products
-    auto load_row = [&](int r) {  // gradient row r: LDS -> X, Y (PP: the products -> Pn)
-      if constexpr (PP) {
+    f32x2 X[NVP / 2], Y[NVP / 2];                  // the next row's gradients
+    auto load_row = [&](int r) {  // gradient row r: LDS -> X, Y
+      const float4* rx = reinterpret_cast<const float4*>(&s_g[0][RPT * rq + r][4 * tq]);
+      const float4* ry = reinterpret_cast<const float4*>(&s_g[1][RPT * rq + r][4 * tq]);
 #pragma unroll
-        for (int pl = 0; pl < 3; ++pl) {
-          const float4* rp = reinterpret_cast<const float4*>(&s_g[pl][RPT * rq + r][4 * tq]);
-#pragma unroll
-          for (int c4 = 0; c4 < NV4; ++c4) {
-            const float4 a = rp[c4];
-            if (2 * c4 < NP2) Pn[PP ? pl : 0][PP ? 2 * c4 : 0] = f32x2{a.x, a.y};
-            if (2 * c4 + 1 < NP2) Pn[PP ? pl : 0][PP ? 2 * c4 + 1 : 0] = f32x2{a.z, a.w};
-          }
-        }
-      } else {
-        const float4* rx = reinterpret_cast<const float4*>(&s_g[0][RPT * rq + r][4 * tq]);
-        const float4* ry = reinterpret_cast<const float4*>(&s_g[1][RPT * rq + r][4 * tq]);
-#pragma unroll
-        for (int c4 = 0; c4 < NV4; ++c4) {
-          const float4 a = rx[c4], c = ry[c4];
-          X[PP ? 0 : 2 * c4] = f32x2{a.x, a.y};
-          X[PP ? 0 : 2 * c4 + 1] = f32x2{a.z, a.w};
-          Y[PP ? 0 : 2 * c4] = f32x2{c.x, c.y};
-          Y[PP ? 0 : 2 * c4 + 1] = f32x2{c.z, c.w};
-        }
+      for (int c4 = 0; c4 < NV4; ++c4) {
+        const float4 a = rx[c4], c = ry[c4];
+        X[2 * c4] = f32x2{a.x, a.y};
+        X[2 * c4 + 1] = f32x2{a.z, a.w};
+        Y[2 * c4] = f32x2{c.x, c.y};
+        Y[2 * c4 + 1] = f32x2{c.z, c.w};
       }
     };
     auto form_products = [&]() {  // the loaded row becomes the current one
 #pragma unroll
       for (int m = 0; m < NP2; ++m) {
-        if constexpr (PP) {
-#pragma unroll
-          for (int pl = 0; pl < 3; ++pl) P[pl][m] = Pn[PP ? pl : 0][PP ? m : 0];
-        } else {
-          P[0][m] = X[PP ? 0 : m] * X[PP ? 0 : m];
-          P[1][m] = Y[PP ? 0 : m] * Y[PP ? 0 : m];
-          P[2][m] = X[PP ? 0 : m] * Y[PP ? 0 : m];
-        }
+        P[0][m] = X[m] * X[m];
+        P[1][m] = Y[m] * Y[m];
+        P[2][m] = X[m] * Y[m];
       }
     };
     load_row(0);
@@ -738,7 +530,7 @@ __global__ void __launch_bounds__(HarrisShape<F>::NT, HarrisShape<F>::WPE) k_har
       __builtin_amdgcn_sched_barrier(0);
       const f32x2 (&Tk)[KS] = T[ABL == 5 ? 0 : (k & 1)];
 #pragma unroll
-      for (int pl = 0; pl < (HY ? 2 : 3); ++pl)
+      for (int pl = 0; pl < 3; ++pl)
 #pragma unroll
         for (int j = 0; j < KS; ++j)
 #pragma unroll
@@ -753,19 +545,6 @@ __global__ void __launch_bounds__(HarrisShape<F>::NT, HarrisShape<F>::WPE) k_har
               acc[p][pl][q].y = __builtin_fmaf(Tk[j].y, P[pl][m >> 1][m & 1], acc[p][pl][q].y);
             }
           }
-      if constexpr (HY && WB::last_of_row(k)) {
-        // S_xy: gradient row r is tap row r - o of output row o; step s takes column 4tq + s
-        // (the thread's own IxIy product) with the banded taps (MfWin)
-        static_for<RPT>([&](auto oc) {
-          constexpr int o = decltype(oc)::value, dy = r - o;
-          if constexpr (dy >= 0 && dy < KS && (ABL != 2 || dy == 0)) {
-            static_for<MNS>([&](auto sc) {
-              constexpr int st = decltype(sc)::value, ks = dy * MNS + st;
-              macc2[o] = __builtin_amdgcn_mfma_f32_4x4x1f32(tapV[ks / 16], P[2][st >> 1][st & 1], macc2[o], 4, ks % 16, 0);
-            });
-          }
-        });
-      }
     });
     __builtin_amdgcn_sched_barrier(0);
     // 3. R = det - alpha * trace^2 (:71-74), digit-1 histogram of R, R stored as 16-B
@@ -782,8 +561,7 @@ __global__ void __launch_bounds__(HarrisShape<F>::NT, HarrisShape<F>::WPE) k_har
       for (int p = 0; p < NPAIR; ++p)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          const f32x2 sxx = acc[p][0][q], syy = acc[p][1][q];
-          const f32x2 sxy = HY ? f32x2{macc2[HY ? 2 * p : 0][q], macc2[HY ? 2 * p + 1 : 0][q]} : acc[p][2][q];
+          const f32x2 sxx = acc[p][0][q], syy = acc[p][1][q], sxy = acc[p][2][q];
           const f32x2 t1v = sxx * syy;
           const f32x2 t2v = sxy * sxy;
           const f32x2 det = t1v - t2v;
@@ -817,7 +595,6 @@ __global__ void __launch_bounds__(HarrisShape<F>::NT, HarrisShape<F>::WPE) k_har
     };
     if (SFM_INTERIOR(ty0 + TH <= H && tx0 + kHT <= W)) epilogue(std::true_type{});
     else epilogue(std::false_type{});
-    }  // !MF
     if constexpr (ABL == 3) {
       if (tid == 0 && stamp && nst < kStampSlots - 4) stamp[4 + nst] = wall_clock64();
       ++nst;
@@ -924,8 +701,6 @@ template <int KS, int ABL = 0>
 static void launch_ks(HarrisLevels g, int B, const float* gk, float alpha, hipStream_t st) {
   // SFMFEAT_HARRIS_PRIO=1: tile-balancing issue priority (A/B)
   static const int prio = env_int(SFM_DIAG_ENV("SFMFEAT_HARRIS_PRIO"), 0);
-  // SFMFEAT_HARRIS_NPAIR=1: the four-wave form for every level (A/B)
-  static const int npair = env_int(SFM_DIAG_ENV("SFMFEAT_HARRIS_NPAIR"), 2);
   // SFMFEAT_HARRIS_SMALL=t: levels whose 64 x 64 tiles number at most t per resident
   // workgroup (over the batch) take the 64 x 32 form (0: never)
   static const int small = env_int(SFM_DIAG_ENV("SFMFEAT_HARRIS_SMALL"), kHarrisSmallTiles);
@@ -933,37 +708,17 @@ static void launch_ks(HarrisLevels g, int B, const float* gk, float alpha, hipSt
   // SFMFEAT_HARRIS_STAGGER=n: odd workgroups sleep n x 8k cycles before their first tile (A/B)
   static const int stagger = env_int(SFM_DIAG_ENV("SFMFEAT_HARRIS_STAGGER"), 0);
   g.stagger = stagger;
-  // SFMFEAT_HARRIS_PP=1: product planes in LDS (form 3) instead of gradient planes (A/B)
-  static const int pp = env_int(SFM_DIAG_ENV("SFMFEAT_HARRIS_PP"), kHarrisProductPlanes);
-  // SFMFEAT_HARRIS_MF=1: window sums on the matrix pipe (form 4) for the levels that take
-  // form 0; 2: for every level; 3 / 4: S_xy on MFMA beside the VALU (form 5), form-0 levels
-  // / every level
-  static const int mf = env_int(SFM_DIAG_ENV("SFMFEAT_HARRIS_MF"), kHarrisMfma);
-  if constexpr (KS == 7) {  // the alternative forms are built for the 7 x 7 window only
+  if constexpr (KS == 7) {  // the 64 x 32 form is built for the 7 x 7 window only
     // the fused pyramid (levels with down[0] set) is validated in form 0 only
     bool fused = false;
     for (int k = 0; k < g.n; ++k) fused = fused || g.l[k].down[0] != nullptr;
     if (fused) return launch_form<KS, ABL, 0>(g, B, gk, alpha, st);
-#ifdef SFM_ABLATIONS  // the forms measured slower (1, 3, 4, 5): diagnostic build only
-    if (npair == 1) return launch_form<KS, ABL, 1>(g, B, gk, alpha, st);
-    if (mf == 2) return launch_form<KS, ABL, 4>(g, B, gk, alpha, st);
-    if (mf == 4) return launch_form<KS, ABL, 5>(g, B, gk, alpha, st);
-#else
-    (void)npair;
-    (void)pp;
-    (void)mf;
-#endif
     bool sm = small > 0;
     for (int k = 0; k < g.n; ++k) {
       const int64_t t64 = (int64_t)((g.l[k].W + kHT - 1) / kHT) * ((g.l[k].H + kHT - 1) / kHT) * B;
       sm = sm && t64 <= (int64_t)small * 512;
     }
     if (sm) return launch_form<KS, ABL, 2>(g, B, gk, alpha, st);
-#ifdef SFM_ABLATIONS
-    if (pp == 1) return launch_form<KS, ABL, 3>(g, B, gk, alpha, st);
-    if (mf == 1) return launch_form<KS, ABL, 4>(g, B, gk, alpha, st);
-    if (mf == 3) return launch_form<KS, ABL, 5>(g, B, gk, alpha, st);
-#endif
   }
   launch_form<KS, ABL, 0>(g, B, gk, alpha, st);
 }

@@ -474,6 +474,43 @@ struct RowBest {
   int32_t col;   // -1: rejected
   float nndr;
 };
+// The matcher's arithmetic contract with the reference (match.hip's file head), once for every
+// exact kernel.  A row's state is its nearest two squared distances e1 <= e2 and the nearest's
+// index j1, ordered by (distance, index); it starts at (INFINITY, 0x7fffffff, INFINITY).
+// Candidate (d, j) into the state:
+SFM_DEV void top2_update(float d, int j, float& e1, int& j1, float& e2) {
+  if (d < e1 || (d == e1 && j < j1)) {
+    e2 = e1;
+    e1 = d;
+    j1 = j;
+  } else if (d < e2) {
+    e2 = d;
+  }
+}
+// another lane's state (o1, oj, o2) over disjoint candidates into this one's (the step of the
+// kernels' xor-shuffle merges)
+SFM_DEV void top2_merge(float& e1, int& j1, float& e2, float o1, int oj, float o2) {
+  if (o1 < e1 || (o1 == e1 && oj < j1)) {
+    e2 = fminf(e1, o2);
+    e1 = o1;
+    j1 = oj;
+  } else {
+    e2 = fminf(e2, o1);
+  }
+}
+// the row's result: the roots (sqrt is monotone, so the state is kept on squared distances),
+// nndr = d1 / d2 and the ratio test
+SFM_DEV RowBest top2_finish(float e1, int j1, float e2, float ratio) {
+  RowBest rb;
+  rb.col = -1;
+  rb.nndr = 0.0f;
+  const float d1 = sqrtf(e1), d2 = sqrtf(e2);
+  if (d2 > 0.0f) {
+    const float nndr = d1 / d2;
+    if (nndr <= ratio) { rb.col = j1; rb.nndr = nndr; }
+  }
+  return rb;
+}
 void launch_transpose_desc(const float* desc, const int32_t* count, int nimg, int64_t cap,
                            int64_t capP, float* descT, hipStream_t st);
 void launch_match_rows(const float* descT, const int32_t* count, int64_t capP, const int32_t* pairs,

@@ -42,16 +42,6 @@ __global__ void __launch_bounds__(256) k_transpose_desc(const float* __restrict_
   }
 }
 
-SFM_DEV void best_update(float s, int col, float& b1, int& j1, float& b2) {
-  if (s < b1 || (s == b1 && col < j1)) {
-    b2 = b1;
-    b1 = s;
-    j1 = col;
-  } else if (s < b2) {
-    b2 = s;
-  }
-}
-
 __global__ void __launch_bounds__(256) k_match_rows(const float* __restrict__ descT,
                                                     const int32_t* __restrict__ count, int64_t capP,
                                                     const int32_t* __restrict__ pairs, float ratio,
@@ -134,7 +124,7 @@ __global__ void __launch_bounds__(256) k_match_rows(const float* __restrict__ de
       const int col = col0 + 4 * tc + ci;
       if (col < n2) {
 #pragma unroll
-        for (int ri = 0; ri < 4; ++ri) best_update(tot[ri][ci], col, b1[ri], j1[ri], b2[ri]);
+        for (int ri = 0; ri < 4; ++ri) top2_update(tot[ri][ci], col, b1[ri], j1[ri], b2[ri]);
       }
     }
   }
@@ -146,30 +136,14 @@ __global__ void __launch_bounds__(256) k_match_rows(const float* __restrict__ de
       float ob1 = __shfl_xor(b1[ri], off, 16);
       float ob2 = __shfl_xor(b2[ri], off, 16);
       int oj1 = __shfl_xor(j1[ri], off, 16);
-      if (ob1 < b1[ri] || (ob1 == b1[ri] && oj1 < j1[ri])) {
-        b2[ri] = fminf(b1[ri], ob2);
-        b1[ri] = ob1;
-        j1[ri] = oj1;
-      } else {
-        b2[ri] = fminf(b2[ri], ob1);
-      }
+      top2_merge(b1[ri], j1[ri], b2[ri], ob1, oj1, ob2);
     }
   }
   if (tc == 0) {
 #pragma unroll
     for (int ri = 0; ri < 4; ++ri) {
       const int row = row0 + 4 * tr + ri;
-      if (row < n1) {
-        RowBest rb;
-        rb.col = -1;
-        rb.nndr = 0.0f;
-        float d1 = sqrtf(b1[ri]), d2 = sqrtf(b2[ri]);
-        if (d2 > 0.0f) {
-          float nndr = d1 / d2;
-          if (nndr <= ratio) { rb.col = j1[ri]; rb.nndr = nndr; }
-        }
-        rows_out[(int64_t)p * max_rows + row] = rb;
-      }
+      if (row < n1) rows_out[(int64_t)p * max_rows + row] = top2_finish(b1[ri], j1[ri], b2[ri], ratio);
     }
   }
 }

@@ -14,9 +14,10 @@
 //      nearest (argument above k_match_mfma);
 //      a row it can prove unmatched from its two smallest d~ and E (proven_unmatched) gets
 //      its "no match" there; the other rows go to the re-rank's work list;
-//   2. k_match_rerank: the list entries within the row's final threshold recomputed with the
-//      reference's exact float32 pairwise order (8 accumulators), (distance, index) top-2,
-//      ratio test;
+//   2. k_match_rerank<ITEMS>: the list entries within the row's final threshold recomputed
+//      with the reference's exact float32 pairwise order (8 accumulators), (distance, index)
+//      top-2, ratio test — the one exact stage, two rows per wavefront (one under
+//      SFMFEAT_RERANK2=0);
 //   3. k_match_overflow: rows whose list overflowed (runs of near-identical target
 //      descriptors), and rows whose bound E is not finite (an element outside the f16 range
 //      in the row or in the target image, k_match_prep), recomputed exactly over every target.
@@ -157,16 +158,6 @@ SFM_DEV float other_half(float x) {
   return __uint_as_float((threadIdx.x & 32) ? r[0] : r[1]);
 }
 SFM_DEV int other_half(int x) { return __float_as_int(other_half(__int_as_float(x))); }
-
-SFM_DEV void top2_merge(float& b1, int& j1, float& b2, float ob1, int oj1, float ob2) {
-  if (ob1 < b1 || (ob1 == b1 && oj1 < j1)) {
-    b2 = fminf(b1, ob2);
-    b1 = ob1;
-    j1 = oj1;
-  } else {
-    b2 = fminf(b2, ob1);
-  }
-}
 
 // The sweep's certificate that a row fails the ratio test ("Rows the prefilter
 // proves unmatched").  r1 <= r2: the row's two smallest d~ over every target; E2 = 2E, finite.
@@ -851,13 +842,18 @@ __global__ void __launch_bounds__(64 * sweep_waves(STAGE), STAGE == 3 ? 2 : 1) k
 
 // Exact re-rank of the row's final window: the admitted targets whose stored d~ (rounded
 // down) is within the row's final threshold, compacted by a ballot into LDS, then the
-// reference's float32 distance (numpy's pairwise order) of each: one wavefront per query
-// row, eight lanes per candidate — lane l of a group accumulates numpy's accumulator
-// r[l] = sum_i (a[8 i + l] - b[8 i + l])^2 in i order (32-B coalesced reads per group),
-// and the groups' partial sums combine as ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7))
-// by xor shuffles (IEEE addition is commutative, so the shuffle pairing is bitwise the
-// reference's).  Per group a running (distance, index) top-2, merged over the 8 groups ->
-// nndr and the ratio test.
+// reference's float32 distance (numpy's pairwise order) of each, eight lanes per candidate —
+// lane l of a group accumulates numpy's accumulator r[l] = sum_i (a[8 i + l] - b[8 i + l])^2
+// in i order (32-B coalesced reads per group), and the groups' partial sums combine as
+// ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)) by xor shuffles (IEEE addition is
+// commutative, so the shuffle pairing is bitwise the reference's).  Per group a running
+// (distance, index) top-2, merged over the item's groups -> nndr and the ratio test.
+//
+// ITEMS (pair, row) items per wavefront, each on 64 / ITEMS lanes: part h of wave w takes
+// item ITEMS w + h, 8 / ITEMS candidates per step.  2 (one item per half-wave) is the
+// default: half the wavefronts for the same latency chain per item (count, list, ballot,
+// candidate rows); 1 is SFMFEAT_RERANK2=0.
+template <int ITEMS>
 __global__ void __launch_bounds__(256) k_match_rerank(const float* __restrict__ desc,
                                                       const int32_t* __restrict__ count, int64_t cap,
                                                       const int32_t* __restrict__ pairs, int P, float ratio,
@@ -867,106 +863,20 @@ __global__ void __launch_bounds__(256) k_match_rerank(const float* __restrict__ 
                                                       const int* __restrict__ work_count,
                                                       const uint32_t* __restrict__ work_list,
                                                       RowBest* __restrict__ rows_out) {
-  __shared__ uint16_t sJ[4][kCandCap];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int grp = lane >> 3, l8 = lane & 7;
-  // item t of the sweep's work list: a live row that is neither proven unmatched (the sweep
-  // wrote its "no match") nor the exact kernel's; the grid covers every (pair, row) slot
-  const int64_t t = (int64_t)blockIdx.x * 4 + wv;
-  if (t >= *work_count) return;
-  const int64_t w = work_list[t];  // (pair, row)
-  const int p = (int)(w / max_rows), row = (int)(w % max_rows);
-  const int i1 = pairs[2 * p], i2 = pairs[2 * p + 1];
-  const int cw = cand_n[w];
-  const int c0 = cw & 0xffff, c1 = cw >> 16;  // the two half-lists' lengths
-  if (c0 > kHalfCap || c1 > kHalfCap) return;  // k_match_overflow's row
-  const float thr = cand_thr[w];
-  const uint32_t* list = cand + w * kCandCap;
-  const float* A = desc + ((int64_t)i1 * cap + row) * 128;
-  const float* Bd = desc + (int64_t)i2 * cap * 128;
-  float a[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) a[i] = A[8 * i + l8];
-  int nk = 0;  // window members, compacted into sJ[wv] in list order
-  static_assert(kHalfCap % 64 == 0, "whole wavefront passes per half-list");
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int ch = h ? c1 : c0;
-    for (int b0 = 0; b0 < ch; b0 += 64) {
-      const int idx = b0 + lane;
-      const bool in = idx < ch;
-      const uint32_t e = in ? list[h * kHalfCap + idx] : 0u;
-      const bool keep = in && __uint_as_float(e & 0xffff0000u) <= thr;
-      const uint64_t bal = __ballot(keep);
-      if (keep) sJ[wv][nk + __popcll(bal & ((1ull << lane) - 1ull))] = (uint16_t)(e & 0xffffu);
-      nk += __popcll(bal);
-    }
-  }
-  __builtin_amdgcn_wave_barrier();
-  float e1 = INFINITY, e2 = INFINITY;
-  int j1 = 0x7fffffff;
-  for (int s0 = 0; s0 < nk; s0 += 8) {
-    const int s = s0 + grp;
-    const bool ok = s < nk;
-    const int j = ok ? (int)sJ[wv][s] : 0;
-    const float* b = Bd + (int64_t)j * 128;
-    float r = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const float dd = a[i] - b[8 * i + l8];
-      const float sq = dd * dd;
-      r = (i == 0) ? sq : r + sq;
-    }
-    r = r + __shfl_xor(r, 1);  // t01, t23, t45, t67
-    r = r + __shfl_xor(r, 2);  // u0 = t01 + t23, u1 = t45 + t67
-    r = r + __shfl_xor(r, 4);  // u0 + u1
-    if (ok) {
-      if (r < e1 || (r == e1 && j < j1)) { e2 = e1; e1 = r; j1 = j; }
-      else if (r < e2) e2 = r;
-    }
-  }
-#pragma unroll
-  for (int off = 8; off <= 32; off <<= 1) {
-    const float o1 = __shfl_xor(e1, off), o2 = __shfl_xor(e2, off);
-    const int oj = __shfl_xor(j1, off);
-    top2_merge(e1, j1, e2, o1, oj, o2);
-  }
-  if (lane == 0) {
-    RowBest rb;
-    rb.col = -1;
-    rb.nndr = 0.0f;
-    const float d1 = sqrtf(e1), d2 = sqrtf(e2);
-    if (d2 > 0.0f) {
-      const float nndr = d1 / d2;
-      if (nndr <= ratio) { rb.col = j1; rb.nndr = nndr; }
-    }
-    rows_out[w] = rb;
-  }
-}
-
-// As k_match_rerank with two (pair, row) items per wavefront, one per half-wave: half h of
-// wave w takes item 2 w + h, four candidates per step (eight lanes each, the same numpy
-// pairwise order), the top-2 merged over the half's four groups.  Half the wavefronts for the
-// same latency chain per item (count, list, ballot, candidate rows).
-__global__ void __launch_bounds__(256) k_match_rerank2(const float* __restrict__ desc,
-                                                       const int32_t* __restrict__ count, int64_t cap,
-                                                       const int32_t* __restrict__ pairs, int P, float ratio,
-                                                       int max_rows, const uint32_t* __restrict__ cand,
-                                                       const int32_t* __restrict__ cand_n,
-                                                       const float* __restrict__ cand_thr,
-                                                       const int* __restrict__ work_count,
-                                                       const uint32_t* __restrict__ work_list,
-                                                       RowBest* __restrict__ rows_out) {
-  __shared__ uint16_t sJ[4][2][kCandCap];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, hf = lane >> 5, hl = lane & 31;
+  static_assert(ITEMS == 1 || ITEMS == 2, "one item per wavefront or per half-wave");
+  constexpr int LPI = 64 / ITEMS;  // lanes per item
+  constexpr int GPI = LPI / 8;     // candidates per step (eight lanes each)
+  static_assert(kHalfCap % LPI == 0, "whole passes per half-list");
+  __shared__ uint16_t sJ[4][ITEMS][kCandCap];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, hf = lane / LPI, hl = lane % LPI;
   const int grp = hl >> 3, l8 = lane & 7;
-  // items 2 i and 2 i + 1 of the sweep's work list (the live rows that are neither proven
-  // unmatched — the sweep wrote their "no match" — nor the exact kernel's); the grid covers
-  // every (pair, row) slot, and a wavefront beyond the list's end leaves at once
-  const int64_t t = ((int64_t)blockIdx.x * 4 + wv) * 2 + hf;
+  // items ITEMS i .. ITEMS i + ITEMS - 1 of the sweep's work list (the live rows that are
+  // neither proven unmatched — the sweep wrote their "no match" — nor the exact kernel's); the
+  // grid covers every (pair, row) slot, and a wavefront beyond the list's end leaves at once
+  const int64_t t = ((int64_t)blockIdx.x * 4 + wv) * ITEMS + hf;
   bool ok = t < *work_count;
   if (!__any(ok)) return;
-  const int64_t w = ok ? (int64_t)work_list[t] : 0;  // (pair, row) of this half-wave
+  const int64_t w = ok ? (int64_t)work_list[t] : 0;  // (pair, row) of this item
   const int p = (int)(w / max_rows), row = (int)(w % max_rows);
   const int i1 = pairs[2 * p], i2 = pairs[2 * p + 1];
   int c0 = 0, c1 = 0;
@@ -984,13 +894,15 @@ __global__ void __launch_bounds__(256) k_match_rerank2(const float* __restrict__
   float a[16];
 #pragma unroll
   for (int i = 0; i < 16; ++i) a[i] = ok ? A[8 * i + l8] : 0.0f;
-  int nk = 0;  // window members of this half's item, compacted into sJ[wv][hf] in list order
-  const uint64_t hmask = hf ? 0xFFFFFFFF00000000ull : 0x00000000FFFFFFFFull;
+  int nk = 0;  // window members of this item, compacted into sJ[wv][hf] in list order
+  const uint64_t hmask = ITEMS == 1 ? ~0ull : hf ? 0xFFFFFFFF00000000ull : 0x00000000FFFFFFFFull;
+  // the wavefront's items walk in step: the longer of their lists, then of their windows
+  auto item_max = [](int v) { return ITEMS == 1 ? v : max(v, __shfl_xor(v, 32)); };
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
     const int ch = ok ? (h ? c1 : c0) : 0;
-    const int chmax = max(ch, __shfl_xor(ch, 32));  // both halves walk the longer list
-    for (int b0 = 0; b0 < chmax; b0 += 32) {
+    const int chmax = item_max(ch);
+    for (int b0 = 0; b0 < chmax; b0 += LPI) {
       const int idx = b0 + hl;
       const bool in = idx < ch;
       const uint32_t e = in ? list[h * kHalfCap + idx] : 0u;
@@ -1004,8 +916,8 @@ __global__ void __launch_bounds__(256) k_match_rerank2(const float* __restrict__
   __builtin_amdgcn_wave_barrier();
   float e1 = INFINITY, e2 = INFINITY;
   int j1 = 0x7fffffff;
-  const int nkmax = max(nk, __shfl_xor(nk, 32));
-  for (int s0 = 0; s0 < nkmax; s0 += 4) {
+  const int nkmax = item_max(nk);
+  for (int s0 = 0; s0 < nkmax; s0 += GPI) {
     const int sidx = s0 + grp;
     const bool okc = sidx < nk;
     // j = 0 for the group's idle lanes: a valid row (of image 0 for an idle item), whose
@@ -1022,162 +934,15 @@ __global__ void __launch_bounds__(256) k_match_rerank2(const float* __restrict__
     r = r + __shfl_xor(r, 1);  // t01, t23, t45, t67
     r = r + __shfl_xor(r, 2);  // u0 = t01 + t23, u1 = t45 + t67
     r = r + __shfl_xor(r, 4);  // u0 + u1
-    if (okc) {
-      if (r < e1 || (r == e1 && j < j1)) { e2 = e1; e1 = r; j1 = j; }
-      else if (r < e2) e2 = r;
-    }
+    if (okc) top2_update(r, j, e1, j1, e2);
   }
 #pragma unroll
-  for (int off = 8; off <= 16; off <<= 1) {
+  for (int off = 8; off < LPI; off <<= 1) {
     const float o1 = __shfl_xor(e1, off), o2 = __shfl_xor(e2, off);
     const int oj = __shfl_xor(j1, off);
     top2_merge(e1, j1, e2, o1, oj, o2);
   }
-  if (hl == 0 && ok) {
-    RowBest rb;
-    rb.col = -1;
-    rb.nndr = 0.0f;
-    const float d1 = sqrtf(e1), d2 = sqrtf(e2);
-    if (d2 > 0.0f) {
-      const float nndr = d1 / d2;
-      if (nndr <= ratio) { rb.col = j1; rb.nndr = nndr; }
-    }
-    rows_out[w] = rb;
-  }
-}
-
-// Exact re-rank, eight (pair, row) items per wavefront (A/B variant, kRerank8MaxPairs):
-// for launches of few pairs k_match_rerank's wave per row leaves most lanes idle and pays
-// three dependent memory latencies per row with few waves to hide them:
-//   1. the eight rows' counts and final thresholds (lanes 0-7), their list entries (the
-//      eight 512-B lists are contiguous: 16 coalesced loads per lane) and their query rows
-//      (into LDS) are fetched together;
-//   2. the entries whose stored d~ (rounded down) lies within the row's final threshold
-//      are compacted by ballots into the wave's LDS list, in row order;
-//   3. eight lanes per candidate compute the reference's float32 distance (numpy's
-//      pairwise order: lane l accumulates r[l] = sum_i (a[8 i + l] - b[8 i + l])^2 in i
-//      order, and the group combines ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)) by
-//      xor shuffles — IEEE addition is commutative, so the pairing is bitwise numpy's);
-//   4. lane r scans row r's contiguous range of distances for the (distance, index)
-//      top-2 -> nndr and the ratio test.
-constexpr int kRrRows = 8;             // (pair, row) items per wavefront
-// launches of up to this many pairs take k_match_rerank8 (default 0: off).  Alone, a
-// 31-pair match call measured 0.291 ms with it against 0.382 (tools/bench_match.py), but
-// inside bench.py's pipeline the match stage measured 0.253 vs 0.222 ms and the headline
-// 29.7k vs 30.9k img/s, so the wave-per-row kernel is the default; SFMFEAT_RERANK8_MAX=N
-// switches it on for A/B timing
-constexpr int kRerank8MaxPairs = 0;
-__global__ void __launch_bounds__(256) k_match_rerank8(const float* __restrict__ desc,
-                                                      const int32_t* __restrict__ count, int64_t cap,
-                                                      const int32_t* __restrict__ pairs, int P, float ratio,
-                                                      int max_rows, const uint32_t* __restrict__ cand,
-                                                      const int32_t* __restrict__ cand_n,
-                                                      const float* __restrict__ cand_thr,
-                                                      const int* __restrict__ work_count,
-                                                      const uint32_t* __restrict__ work_list,
-                                                      RowBest* __restrict__ rows_out) {
-  __shared__ __attribute__((aligned(16))) float sA[4][kRrRows][128];  // query rows
-  __shared__ uint16_t sL[4][kRrRows * kCandCap];  // window members (target index), row order
-  __shared__ float sDist[4][kRrRows * kCandCap];
-  __shared__ int sBeg[4][kRrRows + 1];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int grp = lane >> 3, l8 = lane & 7;
-  // items t0 .. t0 + 7 of the sweep's work list (the live rows that are neither proven
-  // unmatched nor the exact kernel's); a wavefront beyond the list's end leaves at once
-  const int64_t total = *work_count;
-  const int64_t t0 = ((int64_t)blockIdx.x * 4 + wv) * kRrRows;
-  if (t0 >= total) return;
-  // 1. per-row state on lanes 0..7, then broadcast by shuffles
-  int c_l = 0, ok_l = 0, w_l = 0, i1_l = 0, i2_l = 0, row_l = 0, p_l = 0;
-  float thr_l = 0.0f;
-  if (lane < kRrRows) {
-    if (t0 + lane < total) {
-      w_l = (int)work_list[t0 + lane];  // (pair, row): below 2^31 (match_impl)
-      p_l = w_l / max_rows;
-      row_l = w_l % max_rows;
-      i1_l = pairs[2 * p_l];
-      i2_l = pairs[2 * p_l + 1];
-      c_l = cand_n[w_l];  // half-list lengths, low / high 16 bits
-      thr_l = cand_thr[w_l];
-      ok_l = ((c_l & 0xffff) <= kHalfCap && (c_l >> 16) <= kHalfCap) ? 1 : 0;  // else k_match_overflow's row
-    }
-    if (!ok_l) c_l = 0;
-  }
-  // query rows of the eight items -> LDS (row r: 128 floats; 16 per lane)
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int e = lane * 4 + 256 * q;  // float index in [0, 1024)
-    const int r = e >> 7, k = e & 127;
-    const int ir = __shfl(i1_l, r), rr = __shfl(row_l, r), okr = __shfl(ok_l, r);
-    float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (okr) v = *reinterpret_cast<const float4*>(desc + ((int64_t)ir * cap + rr) * 128 + k);
-    *reinterpret_cast<float4*>(&sA[wv][r][k]) = v;
-  }
-  // 2. list entries of the eight rows, filtered and compacted in row order
-  int nk = 0;
-#pragma unroll 4
-  for (int sidx = 0; sidx < kRrRows * kCandCap / 64; ++sidx) {
-    const int e = sidx * 64 + lane;
-    const int r = e / kCandCap, pos = e % kCandCap;  // r is wave-uniform per sidx
-    const int cr = __shfl(c_l, r);
-    const float tr = __shfl(thr_l, r);
-    const int crh = pos < kHalfCap ? (cr & 0xffff) : (cr >> 16);
-    const int64_t wr = __shfl(w_l, r);
-    const bool valid = (pos & (kHalfCap - 1)) < crh;  // crh = 0 for an idle item
-    const uint32_t ent = valid ? cand[wr * kCandCap + pos] : 0u;
-    const bool keep = valid && __uint_as_float(ent & 0xffff0000u) <= tr;
-    const uint64_t bal = __ballot(keep);
-    if (pos == 0 && lane == (sidx * 64) % 64 && (e % kCandCap) == 0) sBeg[wv][r] = nk;  // row start
-    if (keep) sL[wv][nk + __popcll(bal & ((1ull << lane) - 1ull))] = (uint16_t)(ent & 0xffffu);
-    nk += __popcll(bal);
-  }
-  if (lane == 0) sBeg[wv][kRrRows] = nk;
-  __builtin_amdgcn_wave_barrier();
-  // 3. exact distances, eight candidates per iteration
-  for (int s0 = 0; s0 < nk; s0 += 8) {
-    const int s = s0 + grp;
-    const bool ok = s < nk;
-    const int j = ok ? (int)sL[wv][s] : 0;
-    int r = 0;  // the entry's row: ranges [sBeg[r], sBeg[r + 1]) are in row order
-#pragma unroll
-    for (int k = 1; k < kRrRows; ++k) r += (s >= sBeg[wv][k]) ? 1 : 0;
-    const int i2 = __shfl(i2_l, r);
-    const float* b = desc + ((int64_t)i2 * cap + j) * 128;
-    const float* a = &sA[wv][r][0];
-    float acc = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const float dd = a[8 * i + l8] - (ok ? b[8 * i + l8] : a[8 * i + l8]);
-      const float sq = dd * dd;
-      acc = (i == 0) ? sq : acc + sq;
-    }
-    acc = acc + __shfl_xor(acc, 1);  // t01, t23, t45, t67
-    acc = acc + __shfl_xor(acc, 2);  // u0 = t01 + t23, u1 = t45 + t67
-    acc = acc + __shfl_xor(acc, 4);  // u0 + u1
-    if (ok && l8 == 0) sDist[wv][s] = acc;
-  }
-  __builtin_amdgcn_wave_barrier();
-  // 4. lane r: row r's top-2 over its contiguous range
-  if (lane < kRrRows && ok_l) {
-    float e1 = INFINITY, e2 = INFINITY;
-    int j1 = 0x7fffffff;
-    const int beg = sBeg[wv][lane], end = lane + 1 < kRrRows ? sBeg[wv][lane + 1] : nk;
-    for (int s = beg; s < end; ++s) {
-      const float dd = sDist[wv][s];
-      const int j = (int)sL[wv][s];
-      if (dd < e1 || (dd == e1 && j < j1)) { e2 = e1; e1 = dd; j1 = j; }
-      else if (dd < e2) e2 = dd;
-    }
-    RowBest rb;
-    rb.col = -1;
-    rb.nndr = 0.0f;
-    const float d1 = sqrtf(e1), d2 = sqrtf(e2);
-    if (d2 > 0.0f) {
-      const float nndr = d1 / d2;
-      if (nndr <= ratio) { rb.col = j1; rb.nndr = nndr; }
-    }
-    rows_out[w_l] = rb;
-  }
+  if (hl == 0 && ok) rows_out[w] = top2_finish(e1, j1, e2, ratio);
 }
 
 // Rows whose window overflowed the LDS list (long runs of near-identical target
@@ -1204,8 +969,7 @@ __global__ void __launch_bounds__(256) k_match_overflow(const float* __restrict_
     int j1 = 0x7fffffff;
     for (int j = lane; j < n2; j += 64) {
       const float dd = exact_sqdist(A, Bd + (int64_t)j * 128);
-      if (dd < e1 || (dd == e1 && j < j1)) { e2 = e1; e1 = dd; j1 = j; }
-      else if (dd < e2) e2 = dd;
+      top2_update(dd, j, e1, j1, e2);
     }
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) {
@@ -1213,17 +977,7 @@ __global__ void __launch_bounds__(256) k_match_overflow(const float* __restrict_
       const int oj = __shfl_xor(j1, off);
       top2_merge(e1, j1, e2, o1, oj, o2);
     }
-    if (lane == 0) {
-      RowBest rb;
-      rb.col = -1;
-      rb.nndr = 0.0f;
-      const float d1 = sqrtf(e1), d2 = sqrtf(e2);
-      if (d2 > 0.0f) {
-        const float nndr = d1 / d2;
-        if (nndr <= ratio) { rb.col = j1; rb.nndr = nndr; }
-      }
-      rows_out[(int64_t)p * max_rows + row] = rb;
-    }
+    if (lane == 0) rows_out[(int64_t)p * max_rows + row] = top2_finish(e1, j1, e2, ratio);
   }
 }
 
@@ -1251,10 +1005,6 @@ void launch_match_mfma(const float* desc, const int32_t* count, int64_t cap, int
   static const int stage = [] {
     const char* e = getenv("SFMFEAT_MATCH_STAGE");
     return (e && e[0] == 'r') ? 0 : (e && e[0] == '1') ? 1 : 3;
-  }();
-  static const int rr8_max = [] {  // SFMFEAT_RERANK8_MAX: pair-count switch (A/B timing)
-    const char* e = SFM_DIAG_ENV("SFMFEAT_RERANK8_MAX");
-    return e ? atoi(e) : kRerank8MaxPairs;
   }();
   static const bool use_units = [] {  // SFMFEAT_MATCH_UNITS=0: the per-pair XCD mapping (A/B)
     const char* e = SFM_DIAG_ENV("SFMFEAT_MATCH_UNITS");
@@ -1302,22 +1052,19 @@ void launch_match_mfma(const float* desc, const int32_t* count, int64_t cap, int
     SFM_SWEEP(1, 0);
 #endif
 #undef SFM_SWEEP
-  // two (pair, row) items per wavefront above the eight-item kernel's range (round 4: match
-  // stage 0.229 -> 0.223 ms/step at configs[1]); SFMFEAT_RERANK2=0: one item per wavefront (A/B)
+  // the exact re-rank, four wavefronts per workgroup over every (pair, row) slot: two items per
+  // wavefront (round 4: match stage 0.229 -> 0.223 ms/step at configs[1] against one);
+  // SFMFEAT_RERANK2=0: one item per wavefront (A/B)
   static const int rr2 = [] {
     const char* e = getenv("SFMFEAT_RERANK2");
     return e ? atoi(e) : 1;
   }();
-  if (rr2 && P > rr8_max)
-    hipLaunchKernelGGL(k_match_rerank2, dim3((unsigned)(((int64_t)P * max_rows + 7) / 8)), dim3(256), 0, st, desc,
+  if (rr2)
+    hipLaunchKernelGGL(k_match_rerank<2>, dim3((unsigned)(((int64_t)P * max_rows + 7) / 8)), dim3(256), 0, st, desc,
                        count, cap, pairs, P, ratio, max_rows, cand, cand_n, cand_thr, work_count,
                        work_list, rows);
-  else if (P <= rr8_max)
-    hipLaunchKernelGGL(k_match_rerank8, dim3((unsigned)(((int64_t)P * max_rows + 4 * kRrRows - 1) / (4 * kRrRows))),
-                       dim3(256), 0, st, desc, count, cap, pairs, P, ratio, max_rows, cand, cand_n, cand_thr, work_count,
-                       work_list, rows);
   else
-    hipLaunchKernelGGL(k_match_rerank, dim3((unsigned)(((int64_t)P * max_rows + 3) / 4)), dim3(256), 0, st, desc,
+    hipLaunchKernelGGL(k_match_rerank<1>, dim3((unsigned)(((int64_t)P * max_rows + 3) / 4)), dim3(256), 0, st, desc,
                        count, cap, pairs, P, ratio, max_rows, cand, cand_n, cand_thr, work_count,
                        work_list, rows);
   // the overflow list's length stays on the device: a fixed grid strides over it

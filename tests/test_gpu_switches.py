@@ -3,7 +3,7 @@
 The shipped libsfmfeat.so reads exactly the switches in PRODUCT_SWITCHES (a CPU test,
 tests/test_bench_cpu.py::test_shipped_library_reads_only_product_switches, checks the
 library's strings against this list); the alternatives measured slower for good
-(Harris forms 1/3/4/5, NMS strip shapes, stream-schedule and launch-shape A/Bs) are read only
+(Harris launch shapes, NMS strip shapes, stream-schedule and launch-shape A/Bs) are read only
 by the diagnostic build (make ABLATIONS=1, SFM_DIAG_ENV).  The library reads its switches
 once per process (or per context), so each group of alternatives runs in one child process
 (same GPU, same inputs) and this process holds the defaults:
