@@ -791,8 +791,30 @@ int32_t sfm_debug_ransac_fits(sfm_ctx* ctx, double* F, int32_t* counts, int64_t 
  * its last one failed), for a null start_Rt, or for null hyp or counts with entries > 0. */
 int32_t sfm_debug_pnp_fits(sfm_ctx* ctx, double* hyp, int32_t* counts, double* start_Rt, int64_t entries);
 /* Level l's R maps (what 0) or level images (what 1) of the last extraction -> out [B][h][w]
- * (device, on `stream`; diagnostics). */
+ * (device, on `stream`; diagnostics).  what 2: the level's block-maximum maps as its Harris
+ * launch wrote them -> out [B][sfm_debug_bmax_stride(h, w)], each plane's ceil(h / 4) x (w / 4)
+ * map at its start; SFM_EINVAL when the level wrote none. */
 int32_t sfm_debug_copy_level(sfm_ctx* ctx, int32_t l, int32_t what, float* out, void* stream);
+/* Floats between the block-maximum maps of consecutive h x w planes (w % 4 == 0). */
+int64_t sfm_debug_bmax_stride(int32_t h, int32_t w);
+/* The certified 3x3 NMS's choice of kernel for every later extraction of this process: 1 = the
+ * block-driven kernel wherever the shape allows it (W % 4 == 0, ksize 3), 0 = the band kernel
+ * everywhere, -1 = by the size rule, n >= 2 = the size rule with the constant n, below -1 = as
+ * the library was started (the diagnostic build's SFMFEAT_NMS_BLOCKS, else the size rule).  For the tests: the shipped library does not
+ * read the switch. */
+void sfm_debug_set_nms_blocks(int32_t mode);
+/* Which kernel the size rule picks for a certified h x w level at per-level keypoint capacity
+ * kcap and NMS window ksize: 1 = the block-driven kernel, 0 = the band kernel. */
+int32_t sfm_debug_nms_blocks_rule(int32_t h, int32_t w, int32_t kcap, int32_t ksize);
+/* The certified 3x3 NMS on B host planes R [B][H][W] (W % 4 == 0) with per-plane thresholds
+ * tnms [B] and fallback flags [B] (a flagged plane yields nothing), as sfm_debug_nms: blocks = 0
+ * runs the band kernel, 1 the block-driven kernel on maps computed on the host: each 4 x 4
+ * block's maximum over its in-image pixels (NaN dropped) when inflate = 0, that maximum raised
+ * (+inf on every third block, the next float up elsewhere) when inflate = 1 - any upper bound
+ * must give the same candidates. */
+int32_t sfm_debug_nms_blocks(int32_t device, const float* R, int32_t B, int32_t H, int32_t W, const uint32_t* tnms,
+                             const uint32_t* fallback, int32_t blocks, int32_t inflate, uint64_t* keys_out,
+                             int64_t* counts_out);
 
 
 #ifdef __cplusplus

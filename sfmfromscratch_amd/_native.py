@@ -127,6 +127,11 @@ SIGNATURES = {
                                           _fp, ctypes.c_int32, ctypes.c_int32, _fp, _fp, _i64p]),
     "sfm_debug_nms": (ctypes.c_int32, [ctypes.c_int32, _fp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                        ctypes.c_int32, _vp, ctypes.c_int32, _vp, _i64p]),
+    "sfm_debug_bmax_stride": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32]),
+    "sfm_debug_set_nms_blocks": (None, [ctypes.c_int32]),
+    "sfm_debug_nms_blocks_rule": (ctypes.c_int32, [ctypes.c_int32] * 4),
+    "sfm_debug_nms_blocks": (ctypes.c_int32, [ctypes.c_int32, _fp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                              _vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp, _i64p]),
 }
 
 
@@ -601,6 +606,36 @@ def debug_nms(R: np.ndarray, tnms, ksize: int = 3, tile: bool = False, device: i
     check(load_library().sfm_debug_nms(device, R.ctypes.data_as(_fp), B, H, W, ksize, t.ctypes.data,
                                        int(tile), keys.ctypes.data, cnt.ctypes.data_as(_i64p)))
     return [np.sort(keys[b * H * W: b * H * W + cnt[b]]) for b in range(B)]
+
+
+def debug_nms_blocks(R: np.ndarray, tnms, fallback=None, blocks: bool = True, inflate: bool = False, device: int = 0):
+    """The certified 3x3 NMS of B planes R [B, H, W] f32 (W % 4 == 0) with thresholds tnms [B] and
+    fallback flags [B]: the block-driven kernel on host-computed block maxima (inflate: raised to
+    other upper bounds) or, blocks=False, the band kernel -> list of B sorted uint64 key arrays."""
+    R = np.ascontiguousarray(R, dtype=np.float32)
+    B, H, W = R.shape
+    t = np.ascontiguousarray(tnms, dtype=np.uint32)
+    fb = np.zeros(B, np.uint32) if fallback is None else np.ascontiguousarray(fallback, dtype=np.uint32)
+    assert t.shape == (B,) and fb.shape == (B,)
+    keys = np.zeros(B * H * W, np.uint64)
+    cnt = np.zeros(B, np.int64)
+    check(load_library().sfm_debug_nms_blocks(device, R.ctypes.data_as(_fp), B, H, W, t.ctypes.data, fb.ctypes.data,
+                                              int(blocks), int(inflate), keys.ctypes.data, cnt.ctypes.data_as(_i64p)))
+    return [np.sort(keys[b * H * W: b * H * W + cnt[b]]) for b in range(B)]
+
+
+def set_nms_blocks(mode: int):
+    """sfm_debug_set_nms_blocks: 1 / 0 / -1 (by size) for every later extraction of this process."""
+    load_library().sfm_debug_set_nms_blocks(int(mode))
+
+
+def nms_blocks_rule(h: int, w: int, kcap: int, ksize: int = 3) -> bool:
+    """Whether the size rule gives a certified h x w level the block-driven NMS kernel."""
+    return bool(load_library().sfm_debug_nms_blocks_rule(int(h), int(w), int(kcap), int(ksize)))
+
+
+def bmax_stride(h: int, w: int) -> int:
+    return int(load_library().sfm_debug_bmax_stride(int(h), int(w)))
 
 
 def debug_geom(op: int, rows: np.ndarray, device: int = 0) -> np.ndarray:

@@ -12,6 +12,21 @@ using namespace sfm;
 static_assert(kLayoutMedBins == kMedBins1 && kLayoutCounterStride == kCounterStride &&
                   kLayoutMedianStateBytes == sizeof(MedianState) && kLayoutSelectMaxLevels == kSelectMaxLevels,
               "extract_layout.h mirrors kernels.h");
+static_assert(layout_bmax_stride(1080, 1920) == bmax_plane_stride(1080, 1920) &&
+                  layout_bmax_stride(270, 480) == bmax_plane_stride(270, 480) &&
+                  layout_bmax_stride(70, 132) == bmax_plane_stride(70, 132),
+              "extract_layout.h mirrors kernels.h");
+
+// sfm_debug_set_nms_blocks (debug_nms.hip): the tests' override of SFMFEAT_NMS_BLOCKS, which
+// the shipped library does not read (-2: none)
+static int g_nms_blocks_override = -2;
+void extract_set_nms_blocks(int mode) { g_nms_blocks_override = mode < -1 ? -2 : mode; }
+
+LayoutSwitches extract_layout_switches() {
+  LayoutSwitches s = extract_switches().layout;
+  if (g_nms_blocks_override != -2) s.nms_blocks = g_nms_blocks_override;
+  return s;
+}
 
 const ExtractSwitches& extract_switches() {
   static const ExtractSwitches sw = [] {
@@ -25,6 +40,10 @@ const ExtractSwitches& extract_switches() {
     s.layout.exact_px = env_int(getenv("SFMFEAT_EXACT_PX"), 128);
     // SFMFEAT_SELECT_MERGE=0: one selection launch per caller-stream level
     s.layout.select_merge = env_int(SFM_DIAG_ENV("SFMFEAT_SELECT_MERGE"), 1) != 0;
+    // SFMFEAT_NMS_BLOCKS=0: the band kernel at every level; =1: the block-driven certified NMS
+    // (and Harris's block-maximum map) wherever the shape allows it; =n (n >= 2): the size rule
+    // with the constant n; default: the size rule (extract_layout.h nms_blocks_level)
+    s.layout.nms_blocks = env_int(SFM_DIAG_ENV("SFMFEAT_NMS_BLOCKS"), -1);
     s.fill_launches = env_int(SFM_DIAG_ENV("SFMFEAT_FILL_LAUNCHES"), 0) != 0;
     // Harris launches: one per level, unless SFMFEAT_HARRIS_GROUP=g (g >= 1): levels >= g then
     // share launches (up to kHarrisMaxLevels each).  Off by default: grouping L1-L3 or L2-L3 cut
@@ -49,7 +68,7 @@ const ExtractSwitches& extract_switches() {
 namespace {
 
 int layout_of(sfm_ctx* c, int B, int H, int W, ExtractLayout* y) {
-  if (extract_layout(&c->p, c->kcap, B, H, W, c->serial, extract_switches().layout, y) != SFM_OK)
+  if (extract_layout(&c->p, c->kcap, B, H, W, c->serial, extract_layout_switches(), y) != SFM_OK)
     return set_err(c, SFM_EINVAL, "image too small for the pyramid");
   return SFM_OK;
 }
@@ -80,6 +99,7 @@ struct Extraction {
   bool fused_ok;         // every describe launch so far wrote its operands
   bool counted = false;  // the last level's describe launch wrote the slot counts
   bool gate_released = false;
+  bool mapped[SFM_MAX_LEVELS] = {};  // the level's Harris launch wrote its block-maximum map
 
   template <class T>
   T* at(ExtractBuf b, int64_t off) const {
@@ -87,6 +107,7 @@ struct Extraction {
   }
   float* R(int l) const { return at<float>(kBufR, y.plane[l]); }
   uint64_t* cand(int l) const { return at<uint64_t>(kBufCand, y.plane[l]); }
+  float* bmax(int l) const { return at<float>(kBufBmax, y.bmax[l]); }
   MedianState* med(int l) const { return at<MedianState>(kBufMed, y.state[l]); }
   bool exact(int l) const { return c->exact_select || y.exact[l]; }
   KpList kp(int l) const {
@@ -132,6 +153,17 @@ struct Extraction {
       q.down[0] = q.down[1] = q.down[2] = nullptr;
       if (y.pyr_fused && l == 0)
         for (int k = 0; k < 3; ++k) q.down[k] = const_cast<float*>(lvl[1 + k]);
+    }
+    // The block-maximum map of a level the layout gave one: written by the 64 x 64 form of a
+    // launch of its own, from 16-B aligned planes of R, and only where launch_nms will read it.
+    // By the size rule a level keeps the Harris form it would take without a map; the forced
+    // switch (a diagnostic) makes it take the 64 x 64 form.
+    if (l1 - l0 == 1 && y.bmax[l0] >= 0 && ((uintptr_t)R(l0) & 15) == 0 &&
+        nms_blocks_shape(y.lv[l0].w, c->p.ksize, 0) &&
+        (extract_layout_switches().nms_blocks == 1 || harris_tiles_64(g, B, c->p.gaussian_size))) {
+      g.l[0].bmax = bmax(l0);
+      mapped[l0] = true;
+      c->ex.last_mapped |= 1u << l0;
     }
     ProfilerWs& pr = c->prof;
     if (pr.span_cap > 0) {
@@ -249,7 +281,8 @@ int Extraction::run(const float* imgs) {
     for (int l = l0; l < l1; ++l) {
       if (!exact(l)) {
         StageScope sc(c, SFM_PROF_NMS, st);
-        launch_nms(R(l), med(l), cand(l), candcnt + y.counter[l], B, y.lv[l].h, y.lv[l].w, c->p.ksize, 0, st);
+        launch_nms(R(l), med(l), cand(l), candcnt + y.counter[l], B, y.lv[l].h, y.lv[l].w, c->p.ksize, 0, st, 0,
+                   mapped[l] ? bmax(l) : nullptr);
       }
       if (l < L_aux) {
         if (sw.select_caller) select_level(l, st);
@@ -303,6 +336,7 @@ int extract_impl(sfm_ctx* c, const float* imgs, int B, int H, int W, int32_t* xy
   x.last_B = B;
   x.last_H = H;
   x.last_W = W;
+  x.last_mapped = 0;
   operands_fused_clear(c);  // (a failed or non-fused extraction leaves no fused slots)
   Extraction e{c, sw, y, B, skip, st, xy, desc, conf, count, cap, MatchOperands{nullptr, nullptr, nullptr, nullptr, nullptr, 0}};
   return e.run(imgs);

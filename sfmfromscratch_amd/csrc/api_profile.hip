@@ -104,8 +104,15 @@ int32_t sfm_debug_copy_level(sfm_ctx* c, int32_t l, int32_t what, float* out, vo
   if (!c || !out || l < 0 || l >= c->L || !c->ex.last_B) return SFM_EINVAL;
   ExtractWs& x = c->ex;
   ExtractLayout y;
-  if (extract_layout(&c->p, c->kcap, x.last_B, x.last_H, x.last_W, c->serial, extract_switches().layout, &y) != SFM_OK)
+  if (extract_layout(&c->p, c->kcap, x.last_B, x.last_H, x.last_W, c->serial, extract_layout_switches(), &y) != SFM_OK)
     return SFM_EINVAL;
+  if (what == 2) {  // the block-maximum maps, planes bmax_plane_stride apart
+    if (!((x.last_mapped >> l) & 1u) || y.bmax[l] < 0) return set_err(c, SFM_EINVAL, "the level wrote no block-maximum map");
+    HIPCHK(c, hipMemcpyAsync(out, as<float>(x.buf[kBufBmax]) + y.bmax[l],
+                             (size_t)x.last_B * bmax_plane_stride(y.lv[l].h, y.lv[l].w) * 4, hipMemcpyDeviceToDevice,
+                             (hipStream_t)stream));
+    return SFM_OK;
+  }
   const size_t bytes = (size_t)x.last_B * y.lv[l].h * y.lv[l].w * 4;
   const float* src = what == 0 ? as<float>(x.buf[kBufR]) + y.plane[l]
                                : (l == 0 ? as<float>(x.buf[kBufImg0]) : as<float>(x.buf[kBufLvl]) + y.lvl[l]);

@@ -109,6 +109,7 @@ struct ExtractWs {
   DevBuf xy, desc, conf, count;     // sfm_extract's one-slot table
   int64_t extractions = 0;          // extract_impl calls (SFMFEAT_SKIP leaves the first one whole)
   int last_B = 0, last_H = 0, last_W = 0;  // shape of the last extraction (sfm_debug_*)
+  uint32_t last_mapped = 0;         // bit l: level l's Harris launch of that extraction wrote a block-maximum map
 };
 
 // The matcher's per-descriptor operands and the one record of what they hold.  Every write of
@@ -307,6 +308,10 @@ struct ExtractSwitches {
   int skip;                    // SFMFEAT_SKIP=mask (timing bounds only, results wrong by design)
 };
 const ExtractSwitches& extract_switches();  // api_extract.hip
+// the layout switches with the tests' override of SFMFEAT_NMS_BLOCKS applied (-1: the size rule,
+// 0 / 1 / n >= 2 as the switch; below -1: no override)
+sfm::LayoutSwitches extract_layout_switches();
+void extract_set_nms_blocks(int mode);
 
 // api_extract.hip
 int extract_reserve(sfm_ctx* c, int B, int H, int W);

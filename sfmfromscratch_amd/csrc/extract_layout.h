@@ -40,15 +40,38 @@ enum ExtractBuf {
   kBufKpy,
   kBufKpc,      // f32, same shape
   kBufLc,       // i32 [L][B] keypoint counts per level
+  kBufBmax,     // f32 block-maximum maps of the levels that carry one: [B] planes of ceil(h / 4) x (w / 4)
   kExtractBufs
 };
 
-// the switches that change the layout (SFMFEAT_PYR_FUSED, SFMFEAT_EXACT_PX, SFMFEAT_SELECT_MERGE)
+// the switches that change the layout (SFMFEAT_PYR_FUSED, SFMFEAT_EXACT_PX, SFMFEAT_SELECT_MERGE,
+// SFMFEAT_NMS_BLOCKS)
 struct LayoutSwitches {
   bool pyr_fused = true;
   int exact_px = 128;
   bool select_merge = true;
+  // -1: the size rule below; 0: no level; 1: every level whose shape allows it; n >= 2: the size
+  // rule with the constant n in kNmsBlocksC's place (measurements)
+  int nms_blocks = -1;
 };
+
+// The certified select's volume threshold (api_extract.hip): about vmin pixels of a plane lie at
+// or above its candidate threshold.
+inline int64_t select_vmin(int kcap) { return 65536 > (int64_t)128 * kcap ? 65536 : (int64_t)128 * kcap; }
+
+// Which certified 3x3 NMS a level takes, from sizes only: the block-driven kernel (nms.hip
+// k_nms_blocks, fed by a block-maximum map the Harris launch writes) pays where the pixels that
+// can be candidates, about vmin of them, are a small share of the plane: h w >= kNmsBlocksC vmin.
+// At the share 1 / kNmsBlocksC and below, most 4 x 4 blocks hold none (DESIGN_LOG.md §W).
+constexpr int kNmsBlocksC = 4;
+// floats between the maps of consecutive planes (kernels.h bmax_plane_stride: packed where
+// h % 4 == 0, h w / 4 apart otherwise; each map is ceil(h / 4) x (w / 4), w % 4 == 0)
+constexpr int64_t layout_bmax_stride(int h, int w) { return h % 4 == 0 ? (int64_t)h * w / 16 : (int64_t)h * w / 4; }
+inline bool nms_blocks_shape_ok(int w, int ksize) { return ksize / 2 == 1 && w >= 4 && w % 4 == 0; }
+inline bool nms_blocks_level(int h, int w, int kcap, int ksize, bool exact, int sw) {
+  if (sw == 0 || exact || !nms_blocks_shape_ok(w, ksize)) return false;
+  return sw == 1 || (int64_t)h * w >= (sw > 1 ? sw : kNmsBlocksC) * select_vmin(kcap);
+}
 
 struct ExtractLayout {
   int L = 0;
@@ -71,6 +94,7 @@ struct ExtractLayout {
   // selects them all (SFMFEAT_SERIAL, no aux levels: packed from 0), else one region they use
   // in turn
   int64_t sel[SFM_MAX_LEVELS];
+  int64_t bmax[SFM_MAX_LEVELS];     // kBufBmax; -1: the level carries no block-maximum map
 };
 
 // The pyramid of an H x W image: level sizes, window widths and scales.
@@ -108,7 +132,7 @@ inline int extract_layout(const sfm_params* p, int kcap, int B, int H, int W, bo
                 lv[2].h * 4 == H && lv[2].w * 4 == W && lv[3].h * 8 == H && lv[3].w * 8 == W;
   y.select_merged = sw.select_merge && L - y.L_aux > 1 && L - y.L_aux <= kLayoutSelectMaxLevels;
   const int64_t A0 = (int64_t)H * W, kslots = kcap > 1 ? kcap : 1;
-  int64_t plane = 0, lvl = 0, sel = y.select_merged && y.L_aux == 0 ? 0 : (int64_t)B * A0;
+  int64_t plane = 0, lvl = 0, sel = y.select_merged && y.L_aux == 0 ? 0 : (int64_t)B * A0, bmax = 0;
   y.counter_block = (int64_t)L * B * kLayoutCounterStride;
   for (int l = 0; l < L; ++l) {
     const int64_t n = (int64_t)B * lv[l].h * lv[l].w;
@@ -124,6 +148,11 @@ inline int extract_layout(const sfm_params* p, int kcap, int B, int H, int W, bo
     y.counter[l] = (int64_t)l * B * kLayoutCounterStride;
     y.sel[l] = l < y.L_aux ? 0 : sel;
     if (l >= y.L_aux && y.select_merged) sel += n;
+    y.bmax[l] = -1;
+    if (nms_blocks_level(lv[l].h, lv[l].w, kcap, p->ksize, y.exact[l], sw.nms_blocks)) {
+      y.bmax[l] = bmax;
+      bmax += (int64_t)B * layout_bmax_stride(lv[l].h, lv[l].w);
+    }
   }
   const size_t all = (size_t)plane, rest = (size_t)lvl;  // B (A0 + Arest), B Arest
   // B (A0 + A0 + Arest) selection slots cover both region layouts at any pyramid_scale_factor
@@ -140,6 +169,7 @@ inline int extract_layout(const sfm_params* p, int kcap, int B, int H, int W, bo
   y.bytes[kBufScratch] = sel_slots * 8;
   y.bytes[kBufKpx] = y.bytes[kBufKpy] = y.bytes[kBufKpc] = nk * 4;
   y.bytes[kBufLc] = (size_t)L * B * 4;
+  y.bytes[kBufBmax] = (size_t)bmax * 4;
   return SFM_OK;
 }
 

@@ -550,12 +550,11 @@ __global__ void __launch_bounds__(HarrisShape<F>::NT, HarrisShape<F>::WPE) k_har
     // 3. R = det - alpha * trace^2 (:71-74), digit-1 histogram of R, R stored as 16-B
     //    row segments (a wave writes 8 rows x 128 contiguous bytes per store); a tile wholly
     //    inside the plane counts and stores without per-pixel bounds
-    auto epilogue = [&](auto fullc) {
-      constexpr bool FULL = decltype(fullc)::value;
-      // R of both rows of each accumulator pair at once: the same IEEE operations as the
-      // per-pixel form (t1 = sxx*syy, t2 = sxy*sxy, det = t1 - t2, tr = sxx + syy, tr2 =
-      // tr*tr, at = alpha*tr2, R = det - at), as plain v_pk_mul / v_pk_add (no op_sel)
-      f32x2 Rpk[NPAIR][4];
+    // R of both rows of each accumulator pair at once: the same IEEE operations as the
+    // per-pixel form (t1 = sxx*syy, t2 = sxy*sxy, det = t1 - t2, tr = sxx + syy, tr2 =
+    // tr*tr, at = alpha*tr2, R = det - at), as plain v_pk_mul / v_pk_add (no op_sel)
+    f32x2 Rpk[NPAIR][4];
+    {
       const f32x2 al2 = {alpha, alpha};
 #pragma unroll
       for (int p = 0; p < NPAIR; ++p)
@@ -570,6 +569,42 @@ __global__ void __launch_bounds__(HarrisShape<F>::NT, HarrisShape<F>::WPE) k_har
           const f32x2 at = al2 * tr2;
           Rpk[p][q] = det - at;
         }
+    }
+    // block-maximum map (nms.hip k_nms_blocks): the maximum of this thread's 4 x 4 block of R, an
+    // upper bound of the block's in-image maximum (lanes outside the image can only raise it, so
+    // border tiles mask nothing; only the store is guarded: the block's origin lies inside).
+    // Form 0 and 16-B rows only; once for both epilogue variants
+    if constexpr (VEC && RPT == 4) {
+      const int64_t rel = lvs.l[li].bmax_rel;
+      if (rel != 0) {
+        // eight v_max3_f32: R is arithmetic's result, so a NaN is quiet and max3 drops it (a NaN
+        // is never a candidate); the compiler's fmaxf tree adds canonicalising v_max
+        auto rv = [&](int i) { return Rpk[i >> 3][i & 3][(i >> 2) & 1]; };
+        auto max3 = [](float a, float c, float d) {
+          float r;
+          asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(c), "v"(d));
+          return r;
+        };
+        const float m0 = max3(max3(rv(0), rv(1), rv(2)), max3(rv(3), rv(4), rv(5)), max3(rv(6), rv(7), rv(8)));
+        const float m1 = max3(max3(rv(9), rv(10), rv(11)), max3(rv(12), rv(13), rv(14)), rv(15));
+        const float m = max3(m0, m1, m1);
+        // The plane's map lies at (address of the plane's R >> bmax_shift) + bmax_rel (set by the
+        // launcher): the tile loop has no spare SGPRs for another pointer or the plane index, and
+        // Rp is live in it.  Laundered, so that the sum is formed here, not kept across the loop
+        // (the tile's origin too: from ty0 and tx0, which the epilogue keeps, not from the tile's
+        // row and column, whose registers are free by now)
+        uint64_t rp = (uint64_t)Rp;
+        int tyq = ty0, txq = tx0;
+        int wq = W;
+        asm volatile("" : "+s"(rp), "+s"(tyq), "+s"(txq), "+s"(wq));
+        typedef __attribute__((address_space(1))) float gfloat;
+        gfloat* const mt = reinterpret_cast<gfloat*>((rp >> lvs.l[li].bmax_shift) + (uint64_t)rel) +
+                           ((tyq >> 2) * (wq >> 2) + (txq >> 2));
+        if (ty0 + 4 * rq < H && tx0 + 4 * tq < W) mt[(uint32_t)(rq * (wq >> 2) + tq)] = m;
+      }
+    }
+    auto epilogue = [&](auto fullc) {
+      constexpr bool FULL = decltype(fullc)::value;
 #pragma unroll
       for (int o = 0; o < RPT; ++o) {
         const int gy = ty0 + RPT * rq + o;
@@ -689,6 +724,12 @@ static void launch_form(HarrisLevels g, int B, const float* gk, float alpha, hip
     g.l[k].tiles_x = (g.l[k].W + kHT - 1) / kHT;
     g.l[k].ntiles = g.l[k].tiles_x * ((g.l[k].H + S::TH - 1) / S::TH);
     vec = vec && (g.l[k].W & 3) == 0;
+    // the map's place relative to the shifted address of R (bmax_plane_stride: >> 4 packs the
+    // planes' maps, >> 2 where H % 4 != 0)
+    g.l[k].bmax_shift = g.l[k].H % 4 == 0 ? 4 : 2;
+    g.l[k].bmax_rel = g.l[k].bmax == nullptr || F != 0
+                          ? 0
+                          : (int64_t)((uintptr_t)g.l[k].bmax - ((uintptr_t)g.l[k].R >> g.l[k].bmax_shift));
   }
   const int nwg = harris_plan(g, B, slots2 * S::WPC / 2);
   if (vec)
@@ -697,28 +738,37 @@ static void launch_form(HarrisLevels g, int B, const float* gk, float alpha, hip
     hipLaunchKernelGGL((k_harris<KS, false, ABL, F>), dim3(nwg, B), dim3(S::NT), 0, st, g, gk, alpha);
 }
 
+// The 64 x 32 form (7 x 7 window only): levels whose 64 x 64 tiles number at most `small` per
+// resident workgroup (over the batch), none of them written by form 0 alone — the fused pyramid
+// (down[0] set) and the block-maximum map (bmax set) are
+static bool harris_small_form(const HarrisLevels& g, int B, int ks) {
+  // SFMFEAT_HARRIS_SMALL=t: the tile bound (0: never)
+  static const int small = env_int(SFM_DIAG_ENV("SFMFEAT_HARRIS_SMALL"), kHarrisSmallTiles);
+  if (ks != 7 || small <= 0) return false;
+  for (int k = 0; k < g.n; ++k) {
+    if (g.l[k].down[0] != nullptr || g.l[k].bmax != nullptr) return false;
+    const int64_t t64 = (int64_t)((g.l[k].W + kHT - 1) / kHT) * ((g.l[k].H + kHT - 1) / kHT) * B;
+    if (t64 > (int64_t)small * 512) return false;
+  }
+  return true;
+}
+
+bool harris_tiles_64(const HarrisLevels& g, int B, int ks) {
+  HarrisLevels q = g;
+  for (int k = 0; k < q.n; ++k) q.l[k].bmax = nullptr;
+  return !harris_small_form(q, B, ks);
+}
+
 template <int KS, int ABL = 0>
 static void launch_ks(HarrisLevels g, int B, const float* gk, float alpha, hipStream_t st) {
   // SFMFEAT_HARRIS_PRIO=1: tile-balancing issue priority (A/B)
   static const int prio = env_int(SFM_DIAG_ENV("SFMFEAT_HARRIS_PRIO"), 0);
-  // SFMFEAT_HARRIS_SMALL=t: levels whose 64 x 64 tiles number at most t per resident
-  // workgroup (over the batch) take the 64 x 32 form (0: never)
-  static const int small = env_int(SFM_DIAG_ENV("SFMFEAT_HARRIS_SMALL"), kHarrisSmallTiles);
   g.prio = prio;
   // SFMFEAT_HARRIS_STAGGER=n: odd workgroups sleep n x 8k cycles before their first tile (A/B)
   static const int stagger = env_int(SFM_DIAG_ENV("SFMFEAT_HARRIS_STAGGER"), 0);
   g.stagger = stagger;
-  if constexpr (KS == 7) {  // the 64 x 32 form is built for the 7 x 7 window only
-    // the fused pyramid (levels with down[0] set) is validated in form 0 only
-    bool fused = false;
-    for (int k = 0; k < g.n; ++k) fused = fused || g.l[k].down[0] != nullptr;
-    if (fused) return launch_form<KS, ABL, 0>(g, B, gk, alpha, st);
-    bool sm = small > 0;
-    for (int k = 0; k < g.n; ++k) {
-      const int64_t t64 = (int64_t)((g.l[k].W + kHT - 1) / kHT) * ((g.l[k].H + kHT - 1) / kHT) * B;
-      sm = sm && t64 <= (int64_t)small * 512;
-    }
-    if (sm) return launch_form<KS, ABL, 2>(g, B, gk, alpha, st);
+  if constexpr (KS == 7) {
+    if (harris_small_form(g, B, KS)) return launch_form<KS, ABL, 2>(g, B, gk, alpha, st);
   }
   launch_form<KS, ABL, 0>(g, B, gk, alpha, st);
 }

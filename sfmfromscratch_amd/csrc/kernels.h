@@ -375,6 +375,15 @@ struct HarrisLevels {
     // fused pyramid (64 x 64 tiles, H and W multiples of 8): the three exact 2x levels below
     // this one, written from the image tile in LDS (nullptr: none)
     float* down[3];
+    // block-maximum map (64 x 64 tiles, W % 4 == 0): [B][ceil(H / 4)][W / 4], an upper bound of
+    // the maximum of R over each 4 x 4 block, for nms.hip's k_nms_blocks (nullptr: not written)
+    // Planes bmax_plane_stride(H, W) floats apart; R must be 16-B aligned.
+    float* bmax;
+    // filled in by the launcher: plane b's map lies at (address of plane b's R >> bmax_shift) +
+    // bmax_rel bytes (0: no map) — the kernel's tile loop holds the plane's R pointer and has no
+    // SGPRs left for another
+    int64_t bmax_rel;
+    int bmax_shift;
   } l[kHarrisMaxLevels];
   int n;
   int prio;  // 1: waves raise their issue priority with the tiles they have left (A/B)
@@ -384,8 +393,15 @@ struct HarrisLevels {
   // one atomic min / max per workgroup (the slot starts at {~0, 0})
   unsigned long long* span;
 };
+// floats between the block-maximum maps of consecutive planes (each ceil(H / 4) x (W / 4),
+// W % 4 == 0): the planes' R lie H W floats apart and the kernel shifts R's address, so the maps
+// are packed where H % 4 == 0 and H W / 4 apart otherwise
+constexpr int64_t bmax_plane_stride(int H, int W) { return H % 4 == 0 ? (int64_t)H * W / 16 : (int64_t)H * W / 4; }
 void launch_harris_levels(const HarrisLevels& g, int B, const float* d_gauss, int ks, float alpha,
                           hipStream_t st);
+// true: the launch of these levels takes the 64 x 64 form whether or not a level carries a
+// block-maximum map (a map makes it take that form; this asks what it takes without one)
+bool harris_tiles_64(const HarrisLevels& g, int B, int ks);
 // The Harris launches' tap buffer (d_gauss above): the ks x ks Gaussian taps (row-major) at 0,
 // then from float kHarrisPairOff the window's tap pairs (g[d][j], g[d-1][j]) for d = 0..ks,
 // j < ks (a missing tap row is 0), which the kernel reads as wave-uniform scalar loads.
@@ -412,9 +428,14 @@ void launch_median_exact(const float* R, MedianState* state, uint32_t* list, uns
 // plane.  mode 0 (certified planes): R == window max && key(R) >= tnms; mode 1 (fallback
 // planes): the exact predicate (R == window max, or R == 0 below the median).
 // force_tile: the tiled kernel for the certified 3x3 case too (parity test of both forms)
+// bmax: the level's block-maximum map (HarrisLevels::Level::bmax; any upper bound of each 4 x 4
+// block's maximum): the certified 3x3 case with W % 4 == 0 then reads only the blocks that can
+// hold a candidate (k_nms_blocks); nullptr: every pixel (k_nms_band)
 void launch_nms(const float* R, const MedianState* state, uint64_t* cand,
                 unsigned long long* cand_count, int B, int H, int W, int ksize, int mode, hipStream_t st,
-                int force_tile = 0);
+                int force_tile = 0, const float* bmax = nullptr);
+// whether launch_nms takes k_nms_blocks for this call when given a map
+bool nms_blocks_shape(int W, int ksize, int mode);
 
 // select.hip: keypoint selection of one level, one workgroup per plane: top-k by (conf
 // desc, index asc) of the certified NMS candidates + edge filter (NaiveSIFT.py:99-120);

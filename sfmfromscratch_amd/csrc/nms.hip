@@ -438,6 +438,107 @@ __global__ void __launch_bounds__(NT) k_nms_band(const float* __restrict__ R, co
   }
 }
 
+// k_nms_blocks (certified 3x3, W % 4 == 0, levels whose Harris launch wrote a block-maximum
+// map): only a pixel with R >= T can be a candidate, and at the large levels a few percent of
+// the pixels are, so per 4 x 4 block one thread reads the block's entry of the
+// map M — any upper bound of the block's maximum — and only where M >= T its 6 x 6 neighbourhood
+// of R (per row one 16-B load and the two outer columns, -inf outside the image) for the band
+// kernel's predicate on its 16 pixels.  A block with M < T holds no pixel >= T, so the candidate
+// set is k_nms_band's; blocks below T cost their map entry alone.  Appended as there: one atomic
+// per workgroup and pass, the key re-read from R.  The planes' maps lie bmax_plane_stride(H, W) floats apart.
+template <int NT, int BPT>
+__global__ void __launch_bounds__(NT) k_nms_blocks(const float* __restrict__ R, const float* __restrict__ M,
+                                                    const MedianState* __restrict__ st, uint64_t* __restrict__ cand,
+                                                    unsigned long long* __restrict__ cand_count, int H, int W) {
+  const int b = blockIdx.y;
+  if (st[b].fallback != 0) return;  // whole workgroup: fallback planes take the exact path
+  const uint32_t tnms = st[b].tnms;
+  // as k_nms_band: T = fkey_inv(tnms), -inf below the keys' range (every value passes), NaN above it
+  const float T = tnms <= 0x007FFFFFu ? -INFINITY : tnms > 0xFF800000u ? __uint_as_float(0x7FC00000u) : fkey_inv(tnms);
+  const int64_t n = (int64_t)H * W;
+  const float* Rp = R + (int64_t)b * n;
+  const int MW = W >> 2, MH = (H + 3) >> 2;
+  const int64_t nblk = (int64_t)MH * MW;
+  __shared__ uint32_t s_wsum[NT / 64];
+  __shared__ unsigned long long s_base;
+  // The workgroup's BPT * NT consecutive blocks (row-major): every thread reads BPT entries of
+  // the map (all in flight) and lists the blocks that reach T in LDS; then the listed blocks are
+  // shared out one per thread, NT at a time, so the waves that load R are full ones however few
+  // blocks reach T (about one in ten at the first level of a 1080p frame: one thread per block
+  // left each wave waiting on R for a handful of lanes)
+  __shared__ uint32_t s_list[BPT * NT];
+  __shared__ uint32_t s_n;
+  if (threadIdx.x == 0) s_n = 0u;
+  __syncthreads();
+  const int64_t g0 = (int64_t)blockIdx.x * (BPT * NT);
+  const float* Mp = M + (int64_t)b * bmax_plane_stride(H, W);
+  float mv[BPT];
+#pragma unroll
+  for (int k = 0; k < BPT; ++k) {
+    const int64_t g = g0 + k * NT + threadIdx.x;
+    mv[k] = Mp[g < nblk ? g : nblk - 1];
+  }
+#pragma unroll
+  for (int k = 0; k < BPT; ++k) {
+    const int64_t g = g0 + k * NT + threadIdx.x;
+    if (g < nblk && mv[k] >= T) s_list[atomicAdd(&s_n, 1u)] = (uint32_t)(k * NT + threadIdx.x);
+  }
+  __syncthreads();
+  const uint32_t nlist = s_n;  // (the order of the list, and so of the candidates, is any: k_select sorts)
+  for (uint32_t i0 = 0; i0 < nlist; i0 += NT) {  // uniform trip count: barriers inside
+    int by = 0, bx = 0;
+    uint32_t flags = 0;  // bit 4 i + e: pixel (4 by + i, 4 bx + e)
+    if (i0 + threadIdx.x < nlist) {
+      const int64_t g = g0 + s_list[i0 + threadIdx.x];
+      by = (int)(g / MW);
+      bx = (int)(g - (int64_t)by * MW);
+      const float* colp = Rp + 4 * bx;
+      const int lo = bx > 0 ? -1 : 0, ro = bx < MW - 1 ? 4 : 3;  // the outer columns (clamped addresses)
+      float4 q[6];
+      float l[6], r[6];
+#pragma unroll
+      for (int j = 0; j < 6; ++j) {  // every load in flight
+        const float* rp = colp + (int64_t)min(max(4 * by - 1 + j, 0), H - 1) * W;
+        q[j] = *reinterpret_cast<const float4*>(rp);
+        l[j] = rp[lo];
+        r[j] = rp[ro];
+      }
+      float hm[6][4];
+#pragma unroll
+      for (int j = 0; j < 6; ++j) {
+        const int gy = 4 * by - 1 + j;
+        if (gy < 0 || gy >= H) q[j] = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+        const float lv = (bx > 0 && gy >= 0 && gy < H) ? l[j] : -INFINITY;
+        const float rv = (bx < MW - 1 && gy >= 0 && gy < H) ? r[j] : -INFINITY;
+        hm[j][0] = fmaxf(fmaxf(lv, q[j].x), q[j].y);
+        hm[j][1] = fmaxf(fmaxf(q[j].x, q[j].y), q[j].z);
+        hm[j][2] = fmaxf(fmaxf(q[j].y, q[j].z), q[j].w);
+        hm[j][3] = fmaxf(fmaxf(q[j].z, q[j].w), rv);
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float c[4] = {q[i + 1].x, q[i + 1].y, q[i + 1].z, q[i + 1].w};
+        const bool inside = 4 * by + i < H;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float m = fmaxf(fmaxf(hm[i][e], hm[i + 1][e]), hm[i + 2][e]);
+          flags |= (inside && c[e] >= T && c[e] == m) ? (1u << (4 * i + e)) : 0u;
+        }
+      }
+    }
+    if (!__syncthreads_or(flags != 0)) continue;
+    const int64_t slot = block_append(&cand_count[(int64_t)b * kCounterStride], (uint32_t)__popc(flags), s_wsum, &s_base);
+    uint64_t* out = cand + (int64_t)b * n + slot;
+    while (flags) {  // the few candidates re-read their value (an L1 hit)
+      const int bit = __builtin_ctz(flags);
+      flags &= flags - 1;
+      const uint32_t idx = (uint32_t)((4 * by + (bit >> 2)) * W + 4 * bx + (bit & 3));
+      *out++ = ((uint64_t)(~fkey(Rp[idx])) << 32) | idx;
+    }
+  }
+}
+
+constexpr int kNmsBlocksPerThread = 4;  // map entries per k_nms_blocks thread
 constexpr int kStreamSH = 8;
 constexpr int kBandStrips = 4;  // strips of 8 rows per k_nms_band thread (SFMFEAT_NMS_BAND=0: k_nms_stream)
 
@@ -519,11 +620,22 @@ __global__ void __launch_bounds__(256) k_nms_generic(const float* __restrict__ R
   }
 }
 
+bool nms_blocks_shape(int W, int ksize, int mode) {
+  return ksize / 2 == 1 && mode == 0 && W >= 4 && (W & 3) == 0 && !nms_tile_forced();
+}
+
 template <int KH>
 static void launch_tile(const float* R, const MedianState* state, uint64_t* cand, unsigned long long* cnt,
-                        int B, int H, int W, int tiles_x, int mode, hipStream_t st, int force_tile) {
+                        int B, int H, int W, int tiles_x, int mode, hipStream_t st, int force_tile, const float* bmax) {
   const bool vec = (W & 3) == 0;
   if (KH == 1 && mode == 0 && vec && !force_tile && !nms_tile_forced()) {
+    if (bmax != nullptr) {
+      const int64_t nblk = (int64_t)((H + 3) >> 2) * (W >> 2);
+      hipLaunchKernelGGL((k_nms_blocks<256, kNmsBlocksPerThread>),
+                         dim3((unsigned)((nblk + 256 * kNmsBlocksPerThread - 1) / (256 * kNmsBlocksPerThread)), B), dim3(256),
+                         0, st, R, bmax, state, cand, cnt, H, W);
+      return;
+    }
     // SFMFEAT_NMS_SH=8: 8-row strips (A/B); SFMFEAT_NMS_DRY=1: a candidate-free read pass
     // of R ahead of the real one (timing only: how fast R reads once Harris's writes drained)
     static const int sh = [] { const char* e = SFM_DIAG_ENV("SFMFEAT_NMS_SH"); return e ? atoi(e) : kStreamSH; }();
@@ -580,17 +692,17 @@ static void launch_tile(const float* R, const MedianState* state, uint64_t* cand
 
 void launch_nms(const float* R, const MedianState* state, uint64_t* cand,
                 unsigned long long* cand_count, int B, int H, int W, int ksize, int mode, hipStream_t st,
-                int force_tile) {
+                int force_tile, const float* bmax) {
   const int kh = ksize / 2;
   const int tiles_x = (W + kNT_W - 1) / kNT_W;
   const int tiles_y = (H + kNT_H - 1) / kNT_H;
   const int ntiles = tiles_x * tiles_y;
   switch (kh) {
-    case 0: launch_tile<0>(R, state, cand, cand_count, B, H, W, tiles_x, mode, st, force_tile); break;
-    case 1: launch_tile<1>(R, state, cand, cand_count, B, H, W, tiles_x, mode, st, force_tile); break;
-    case 2: launch_tile<2>(R, state, cand, cand_count, B, H, W, tiles_x, mode, st, force_tile); break;
-    case 3: launch_tile<3>(R, state, cand, cand_count, B, H, W, tiles_x, mode, st, force_tile); break;
-    case 4: launch_tile<4>(R, state, cand, cand_count, B, H, W, tiles_x, mode, st, force_tile); break;
+    case 0: launch_tile<0>(R, state, cand, cand_count, B, H, W, tiles_x, mode, st, force_tile, bmax); break;
+    case 1: launch_tile<1>(R, state, cand, cand_count, B, H, W, tiles_x, mode, st, force_tile, bmax); break;
+    case 2: launch_tile<2>(R, state, cand, cand_count, B, H, W, tiles_x, mode, st, force_tile, bmax); break;
+    case 3: launch_tile<3>(R, state, cand, cand_count, B, H, W, tiles_x, mode, st, force_tile, bmax); break;
+    case 4: launch_tile<4>(R, state, cand, cand_count, B, H, W, tiles_x, mode, st, force_tile, bmax); break;
     default: {
       dim3 grid(std::min(ntiles, kNmsBlocksPerPlane), B);
       hipLaunchKernelGGL(k_nms_generic<SFM_NMS_MAX_HALF>, grid, dim3(256), 0, st, R, state, cand, cand_count, H, W,
