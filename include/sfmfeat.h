@@ -421,7 +421,8 @@ int32_t sfm_bundle_adjust_dev(sfm_ctx* ctx, const int32_t* cam_idx, const int32_
 /* Feature tracks: the connected components of the match graph of a slot table, the step between
  * pairwise matches and reconstruction in COLMAP / OpenMVG / openMVS.  The reference has none; the
  * rule is the library's own, pinned to a numpy restatement and scipy's connected_components
- * (DESIGN.md §13F).  No geometric verification is built in: `keep` carries the caller's.
+ * (DESIGN.md §13F).  `keep` carries the geometric verification: sfm_verify_matches_dev (below)
+ * writes it on the device in exactly this layout, and a caller may pass a mask of its own.
  * Inputs (device), in the layouts of sfm_match_pairs_dev: count [nimg], pairs [P][2],
  * matches [P][cap][2], nmatch [P]; keep [P][cap] uint8 (optional; NULL: every match counts).
  *  Nodes: (slot s, row r) with r < count[s] (count clamped to [0, cap]); id = s * cap + r.
@@ -448,6 +449,59 @@ int32_t sfm_build_tracks_dev(sfm_ctx* ctx, const int32_t* count, int32_t nimg, i
                              int32_t P, const int32_t* matches, const int32_t* nmatch, const uint8_t* keep,
                              int32_t min_len, int32_t* track_offsets, int32_t* obs_slot, int32_t* obs_row,
                              int32_t* node_track, int32_t* out_n, void* stream);
+
+/* Two-view geometric verification of the matches of a pair schedule, the step COLMAP and OpenMVG
+ * put between matching and tracks: an 8-point RANSAC per pair whose inlier mask is the `keep` of
+ * sfm_build_tracks_dev.  The reference has none; the rule is the library's own, pinned to a numpy
+ * restatement (tests/verify_ref.py).
+ * Inputs (device), exactly as sfm_match_pairs_dev leaves them: xy [nimg][cap][2] int32 and
+ * count [nimg] of the slot table, pairs [P][2], matches [P][cap][2], nmatch [P].
+ * For pair p with slots (a, b) = pairs[p] and n = clamp(nmatch[p], 0, cap) (nmatch = -1 counts as 0):
+ *  Candidates: match m < n is valid when both rows lie in [0, count) of their slots (count
+ *   clamped to [0, cap]); its correspondence is (xy[a][matches[p][m][0]], xy[b][matches[p][m][1]]).
+ *   An invalid match is never an inlier and never kept; a sample that contains one counts 0.  The
+ *   pair is not attempted when a slot is outside [0, nimg), when a == b or when n < 8: then
+ *   stat = {-1, -1, 0, 0}, keep all 0, F all NaN.
+ *  Samples: counter-based, integers only, a function of (seed, a, b, it) and nothing else (not of
+ *   P, of the pair's position in the call or of the other pairs).  mix64 is the splitmix64
+ *   finaliser (z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB;
+ *   z ^= z >> 31), G = 0x9E3779B97F4A7C15, all in uint64: key = mix64(mix64(seed) + ((a << 32) | b));
+ *   draw k = 0..7 of sample it is r = mix64(key + (8 it + k + 1) G) >> 32.  The eight indices come
+ *   from a Fisher-Yates over a virtual arange(n): j = k + ((r (n - k)) >> 32), the sample's k-th
+ *   index is the value now at position j, then positions k and j are swapped.  The indices are
+ *   distinct and in [0, n) for every n >= 8.
+ *  Fit and test: F per sample by the route of sfm_ransac_find_inliers (Hartley normalisation,
+ *   elimination with partial pivoting, the last free column set to 1, rank 2 by Jacobi,
+ *   un-normalisation) and that call's inlier test d = |l . p2| / sqrt(l0^2 + l1^2) < threshold,
+ *   l = F p1, float64.  A threshold that is <= 0 or NaN admits nothing.
+ *  Rounds and early stop: samples are evaluated in rounds of 256 (the round size is part of the
+ *   rule): round r = 1, 2, ... holds samples 256 (r - 1) .. min(iters, 256 r) - 1.  After round r,
+ *   with `best` the largest count so far, the pair stops when r <= n_stop and
+ *   (double)best >= stop_ratio[r - 1] * (double)n (one IEEE multiply, one compare); otherwise
+ *   after the last round.  stop_ratio is a HOST array of n_stop <= 64 doubles, copied into the
+ *   kernel's arguments before the call returns; n_stop = 0 means fixed iterations.
+ *  Winner: the lowest it among the evaluated samples with the largest count.  The pair is
+ *   verified when that count is > 0 and >= min_inliers.  For a verified pair keep[p][m] = 1
+ *   exactly for the valid matches that are inliers of the winner's F (the same test and the same F
+ *   that produced the count, so the row holds exactly `count` ones); otherwise the row is all 0.
+ *   Every one of the cap bytes of keep[p] is written, 0 at and beyond n.
+ * Outputs (device): keep [P][cap] uint8; F [P][9] float64, the winner's whether or not the pair
+ * is verified (scale and sign unspecified; NaN when no sample had an inlier); stat [P][4] int32 =
+ * best count, winning sample, samples evaluated, verified (0/1).  iters == 0: every attempted pair
+ * gets {0, -1, 0, 0}.
+ * Two runs write the same bytes; permuting the pairs, or splitting a schedule over several calls,
+ * gives each pair the same bytes.  The order of the matches WITHIN a pair does matter: the sample
+ * indices address it.  No refit on the inliers, no homography / degeneracy model selection, no
+ * guided matching.  One launch enqueued on `stream`: no workspace, no allocation, no
+ * synchronisation, no device read of host memory, so the call can be captured into a hipGraph.
+ * SFM_EINVAL: nimg or cap < 1, P < 0, iters outside [0, 2^20], n_stop outside [0, 64], stop_ratio
+ * null with n_stop > 0, min_inliers < 0, a null pointer (but every array indexed by p when
+ * P == 0). */
+int32_t sfm_verify_matches_dev(sfm_ctx* ctx, const int32_t* xy, const int32_t* count, int32_t nimg, int64_t cap,
+                               const int32_t* pairs, int32_t P, const int32_t* matches, const int32_t* nmatch,
+                               int32_t iters, double threshold, int32_t min_inliers, int64_t seed,
+                               const double* stop_ratio, int32_t n_stop, uint8_t* keep, double* F, int32_t* stat,
+                               void* stream);
 
 /* Each track's 3-D point from all its views: CameraPose.triangulate_point (SFM.py:241-246)
  * extended from 2 to V views.  track_offsets / obs_slot / obs_row: the CSR of

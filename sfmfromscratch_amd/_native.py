@@ -79,6 +79,11 @@ SIGNATURES = {
                                                ctypes.c_int32, _vp, ctypes.c_double, ctypes.c_int32, _vp, _vp, _vp,
                                                _vp, _vp]),
     **_abi.TRACK_SIGNATURES,  # sfm_build_tracks_dev, sfm_triangulate_tracks_dev
+    # ctx, xy, count, nimg, cap, pairs, P, matches, nmatch, iters, threshold, min_inliers, seed,
+    # stop_ratio (host), n_stop, keep, F, stat, stream
+    "sfm_verify_matches_dev": (ctypes.c_int32, [_vp, _vp, _vp, ctypes.c_int32, ctypes.c_int64, _vp, ctypes.c_int32,
+                                                _vp, _vp, ctypes.c_int32, ctypes.c_double, ctypes.c_int32,
+                                                ctypes.c_int64, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp]),
     "sfm_ingest_rgb_dev": (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                             ctypes.c_int32, ctypes.c_int32, _vp, _vp]),
     "sfm_extract_batch_dev": (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp,
@@ -546,6 +551,29 @@ class Context:
                 tp(obs_row, "int32", N, "obs_row"), tp(node_track, "int32", N, "node_track"),
                 tp(out_n, "int32", 6, "out_n")]
         check(self.lib.sfm_build_tracks_dev(self.handle, *args, stream or None), self.handle)
+
+    def verify_matches_dev(self, xy, count, pairs, matches, nmatch, iters: int, threshold: float, min_inliers: int,
+                           seed: int, stop_ratio, keep, F, stat, stream: int = 0):
+        """sfm_verify_matches_dev over device tensors (include/sfmfeat.h has the rule): xy [nimg, cap, 2]
+        and count [nimg] int32 of the slot table, pairs [P, 2], matches [P, cap, 2], nmatch [P] int32;
+        stop_ratio a host sequence of at most 64 floats (None or empty: fixed iterations); outputs
+        keep [P, cap] uint8, F [P, 9] float64, stat [P, 4] int32."""
+        if len(getattr(xy, "shape", ())) != 3 or xy.shape[2] != 2:
+            raise ValueError("xy must be [nimg, cap, 2]")
+        nimg, cap = int(xy.shape[0]), int(xy.shape[1])
+        P = int(pairs.shape[0]) if pairs is not None and hasattr(pairs, "shape") and len(pairs.shape) == 2 else 0
+        if pairs is not None and tuple(getattr(pairs, "shape", ())) != (P, 2):
+            raise ValueError("pairs must be [P, 2]")
+        sr = np.ascontiguousarray(np.asarray([] if stop_ratio is None else stop_ratio, np.float64).reshape(-1))
+        tp = self._tensor_ptr
+        args = [tp(xy, "int32", nimg * cap * 2, "xy"), tp(count, "int32", nimg, "count"), nimg, cap,
+                tp(pairs, "int32", 2 * P, "pairs", optional=P == 0), P,
+                tp(matches, "int32", 2 * P * cap, "matches", optional=P == 0),
+                tp(nmatch, "int32", P, "nmatch", optional=P == 0), int(iters), float(threshold), int(min_inliers),
+                int(seed), sr.ctypes.data if len(sr) else None, len(sr),
+                tp(keep, "uint8", P * cap, "keep", optional=P == 0), tp(F, "float64", 9 * P, "F", optional=P == 0),
+                tp(stat, "int32", 4 * P, "stat", optional=P == 0)]
+        check(self.lib.sfm_verify_matches_dev(self.handle, *args, stream or None), self.handle)
 
     def triangulate_tracks_dev(self, track_offsets, obs_slot, obs_row, n_tracks: int, n_obs: int, xy, P, cam_valid,
                                X, out_views, stream: int = 0):

@@ -207,6 +207,19 @@ void launch_ransac(const int32_t* pts, const int32_t* npts, int nmax, int P, con
                    int32_t* out_n, int32_t* out_iter, hipStream_t st);
 constexpr int kRansacChunk = 2560;  // points staged in LDS at a time (32 B each)
 
+// verify.hip: sfm_verify_matches_dev (include/sfmfeat.h has the rule).  The stop table goes to
+// the kernel by value, so the call reads no host memory after it returns.
+constexpr int kVerifyRound = 256;   // samples per round: part of the rule
+constexpr int kVerifyMaxStop = 64;  // rounds that can carry a stop ratio
+constexpr int kVerifyMaxIters = 1 << 20;
+struct VerifyStop {
+  double ratio[kVerifyMaxStop];
+  int n;
+};
+void launch_verify(const int32_t* xy, const int32_t* count, int nimg, int64_t cap, const int32_t* pairs, int P,
+                   const int32_t* matches, const int32_t* nmatch, int iters, double thr, int min_inliers,
+                   uint64_t seed, const VerifyStop& stop, uint8_t* keep, double* F, int32_t* stat, hipStream_t st);
+
 // pose.hip: CameraPose.ransac_camera_motion (SFM.py:38-124) on top of the RANSAC launches, and
 // triangulate_point / triangulate_points (SFM.py:239-253, 292-305).  Kc [P][2][9] (K1, K2),
 // base [P][12] (R_base, T_base), cand [P][iters][21] (R1, R2, T), cand_idx [P][iters] (the

@@ -38,6 +38,17 @@ def calculate_num_ransac_iterations(prob_success: float, sample_size: int, ind_p
     return int(num_samples)
 
 
+def ransac_stop_ratios(confidence: float, rounds: int) -> np.ndarray:
+    """The early-stop table of sequence.verify_matches (sfm_verify_matches_dev's stop_ratio): entry
+    r - 1, r = 1..rounds, is (1 - (1 - confidence)^(1 / (256 r)))^(1 / 8), the inlier ratio w at which
+    256 r eight-point samples contain an all-inlier one with probability `confidence`
+    (1 - (1 - w^8)^(256 r) = confidence).  Pure numpy, float64; strictly decreasing in r."""
+    if not 0.0 < confidence < 1.0:
+        raise ValueError("confidence must lie in (0, 1)")
+    r = np.arange(1, int(rounds) + 1, dtype=np.float64)
+    return (-np.expm1(np.log1p(-np.float64(confidence)) / (256.0 * r))) ** 0.125
+
+
 def sample_indices(n: int, iters: int, seed: int = 5) -> np.ndarray:
     """[iters, 8] int32: np.random.seed(seed); [np.random.choice(n, 8, replace=False) ...]
     (numpy's legacy MT19937 + Fisher-Yates, replayed natively; host only)."""

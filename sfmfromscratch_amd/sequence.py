@@ -367,24 +367,24 @@ class Tracks:
         return cls(up(off), up(s), up(r), up(nt), up(st), xy, int(ml))
 
 
-def _padded_matches(torch, matches, keep, P, cap, dev):
+def _padded_matches(torch, matches, keep, P, cap, dev, who="build_tracks"):
     """The host list of match_schedule (and an optional list of per-pair masks) in the padded
     device layout of sfm_match_pairs_dev: matches [P, cap, 2], nmatch [P], keep [P, cap] or None."""
     if len(matches) != P:
-        raise ValueError("build_tracks: one (matches, confidences) entry per pair")
+        raise ValueError(f"{who}: one (matches, confidences) entry per pair")
     mm = np.zeros((max(P, 1), cap, 2), np.int32)
     nm = np.zeros(max(P, 1), np.int32)
     kk = None if keep is None else np.zeros((max(P, 1), cap), np.uint8)
     for p, entry in enumerate(matches):
         m = np.asarray(entry[0] if isinstance(entry, (tuple, list)) else entry).reshape(-1, 2)
         if len(m) > cap:
-            raise ValueError(f"build_tracks: pair {p} has {len(m)} matches, more than the table's capacity {cap}")
+            raise ValueError(f"{who}: pair {p} has {len(m)} matches, more than the table's capacity {cap}")
         mm[p, :len(m)] = m
         nm[p] = len(m)
         if kk is not None:
             k = np.asarray(keep[p]).reshape(-1)
             if len(k) != len(m):
-                raise ValueError(f"build_tracks: keep[{p}] must have one entry per match of pair {p}")
+                raise ValueError(f"{who}: keep[{p}] must have one entry per match of pair {p}")
             kk[p, :len(m)] = k != 0
     return (torch.from_numpy(mm).to(dev), torch.from_numpy(nm).to(dev),
             None if kk is None else torch.from_numpy(kk).to(dev))
@@ -400,7 +400,8 @@ def build_tracks(cache, pairs, matches, keep=None, min_len: int = 2) -> Tracks:
     the device triple of BatchMatcher.match (matches [P, cap, 2], conf, nmatch), used in place, or
     the host list match_schedule returns, uploaded into that layout.  keep (optional): which
     matches count — [P, cap] (numpy or a device tensor, non-zero = keep), or with a host list one
-    mask per pair; this is where a caller's geometric verification comes in, none is built in.
+    mask per pair; this is where geometric verification comes in: `verify_matches(...).keep_dev`
+    is that mask, computed on the device, and a caller may pass one of its own.
     Enqueued on torch's current stream; nothing synchronises until a host property is read."""
     import torch
     from . import _abi
@@ -439,3 +440,136 @@ def build_tracks(cache, pairs, matches, keep=None, min_len: int = 2) -> Tracks:
         ctx.build_tracks_dev(slots.count, cap, pt, mm, nm, kk, int(min_len), offsets, obs_slot, obs_row, node_track,
                              out_n, stream)
     return Tracks(offsets, obs_slot, obs_row, node_track, out_n, slots.xy, min_len)
+
+
+# ---------------- geometric verification (verify.hip) ----------------
+
+class Verified:
+    """What sfm_verify_matches_dev leaves for a pair schedule (include/sfmfeat.h has the rule).  The
+    device tensors stay resident: `keep_dev` [P, cap] uint8 (the `keep` of build_tracks), `F_dev`
+    [P, 9] float64 (each pair's winning F, NaN where no sample had an inlier), `stat_dev` [P, 4]
+    int32.  The numpy properties copy on first use, which synchronises."""
+
+    def __init__(self, keep, F, stat, pairs, matches, conf, nmatch):
+        self.keep_dev, self.F_dev, self.stat_dev = keep, F, stat
+        self._pairs, self._matches, self._conf, self._nmatch = pairs, matches, conf, nmatch
+        self._host = {}
+
+    def _np(self, key, t):
+        if key not in self._host:
+            self._host[key] = t.cpu().numpy()
+        return self._host[key]
+
+    @property
+    def keep(self) -> np.ndarray:
+        return self._np("keep", self.keep_dev)
+
+    @property
+    def F(self) -> np.ndarray:
+        """[P, 3, 3] float64."""
+        return self._np("F", self.F_dev).reshape(-1, 3, 3)
+
+    @property
+    def stat(self) -> np.ndarray:
+        return self._np("stat", self.stat_dev)
+
+    @property
+    def n_inliers(self) -> np.ndarray:
+        """The winner's inlier count per pair (-1: the pair was not attempted)."""
+        return self.stat[:, 0]
+
+    @property
+    def best_iter(self) -> np.ndarray:
+        return self.stat[:, 1]
+
+    @property
+    def samples(self) -> np.ndarray:
+        """Samples evaluated per pair (fewer than max_iterations where the early stop fired)."""
+        return self.stat[:, 2]
+
+    @property
+    def verified(self) -> np.ndarray:
+        return self.stat[:, 3] != 0
+
+    def inlier_matches(self) -> list:
+        """The host list of match_schedule with only the kept matches of each pair: (matches (k, 2)
+        int64, confidences (k,) float32), the float64 (0,) arrays where nothing is kept.  The
+        confidences are the caller's — the device triple's conf tensor, or the second entries of the
+        host list; only where the caller gave none (a triple with conf=None, a list of bare match
+        arrays) is every confidence 1."""
+        P, keep = len(self.stat), self.keep
+        mm = self._np("matches", self._matches)
+        cc = self._conf
+        if cc is not None and not isinstance(cc, np.ndarray):
+            cc = self._np("conf", cc)
+        out = []
+        for p in range(P):
+            sel = np.flatnonzero(keep[p])
+            if len(sel) == 0:
+                out.append((np.array([]), np.array([])))
+            else:
+                c = np.ones(len(sel), np.float32) if cc is None else cc[p, sel].astype(np.float32)
+                out.append((mm[p, sel].astype(np.int64), c))
+        return out
+
+
+def verify_matches(cache, pairs, matches, threshold: float = 1.0, max_iterations: int | None = None,
+                   confidence: float | None = 0.98, min_inliers: int = 16, seed: int = 5) -> Verified:
+    """Two-view geometric verification of the matches of a pair schedule on the device: an 8-point
+    RANSAC per pair (epipolar distance < `threshold` pixels) whose inlier mask is the `keep` of
+    build_tracks — `build_tracks(cache, pairs, matches, keep=verify_matches(...).keep_dev)`
+    (include/sfmfeat.h sfm_verify_matches_dev has the rule in full).
+
+    cache, pairs, matches: as build_tracks takes them (the device triple of BatchMatcher.match, used
+    in place, or the host list of match_schedule, uploaded).  max_iterations=None is
+    pose.calculate_num_ransac_iterations(0.98, 8, 0.4), the runner's own 5,967.  confidence: a pair
+    stops after a round of 256 samples once its best inlier ratio reaches the ratio at which the
+    samples drawn so far contain an all-inlier one with this probability
+    (pose.ransac_stop_ratios); None or 0 turns the early stop off.  min_inliers: a pair whose
+    winner has fewer inliers keeps nothing; 16, twice the sample size, is this library's own
+    default (the reference has no such step).  Samples depend on (seed, the pair's two slots, the
+    sample's number) only.  Enqueued on torch's current stream; nothing synchronises until a host
+    property of the result is read."""
+    import torch
+    from . import _abi, pose
+    from ._native import context_for
+    slots = getattr(cache, "slots", cache)
+    dev = slots.xy.device
+    nimg, cap = int(slots.count.numel()), int(slots.xy.shape[1])
+    extractor = getattr(cache, "extractor", None)
+    ctx = extractor.ctx if extractor is not None else \
+        context_for(_abi.params_from_dict({}, _abi.SFM_MODE_NAIVE), dev.index or 0)
+    if isinstance(pairs, torch.Tensor):
+        pt = pairs.to(device=dev, dtype=torch.int32).reshape(-1, 2).contiguous()
+    else:
+        pt = torch.from_numpy(np.ascontiguousarray(np.asarray(pairs).reshape(-1, 2), np.int32)).to(dev)
+    P = int(pt.shape[0])
+    iters = pose.calculate_num_ransac_iterations(0.98, 8, 0.4) if max_iterations is None else int(max_iterations)
+    stop = None
+    if confidence:
+        stop = pose.ransac_stop_ratios(float(confidence), min(64, (max(iters, 0) + 255) // 256))
+    with torch.cuda.device(dev):
+        if len(matches) == 3 and isinstance(matches[0], torch.Tensor):
+            mm, cc, nm = matches
+            if mm.dim() != 3 or tuple(mm.shape[1:]) != (cap, 2) or int(mm.shape[0]) < P:
+                raise ValueError(f"verify_matches: matches must be [P, {cap}, 2] for the table's capacity")
+        else:
+            mm, nm, _ = _padded_matches(torch, matches, None, P, cap, dev, who="verify_matches")
+            cc = np.zeros((max(P, 1), cap), np.float32)   # the list's confidences stay on the host
+            for p, entry in enumerate(matches):
+                if isinstance(entry, (tuple, list)) and len(entry) > 1:
+                    c = np.asarray(entry[1], np.float32).reshape(-1)
+                    k = np.asarray(entry[0]).size // 2   # (host counts: nm is on the device already)
+                    if len(c) != k:
+                        raise ValueError(f"verify_matches: pair {p} has {k} matches and {len(c)} confidences")
+                    cc[p, :len(c)] = c
+                else:
+                    cc = None   # a list of bare match arrays carries no confidences
+                    break
+        keep = torch.empty((P, cap), dtype=torch.uint8, device=dev)
+        F = torch.empty((P, 9), dtype=torch.float64, device=dev)
+        stat = torch.empty((P, 4), dtype=torch.int32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        ctx.verify_matches_dev(slots.xy, slots.count, pt, mm, nm, iters, float(threshold), int(min_inliers), int(seed),
+                               stop, keep, F, stat, stream)
+    return Verified(keep, F, stat, pt, mm, cc, nm)
