@@ -491,8 +491,8 @@ int32_t sfm_build_tracks_dev(sfm_ctx* ctx, const int32_t* count, int32_t nimg, i
  * gets {0, -1, 0, 0}.
  * Two runs write the same bytes; permuting the pairs, or splitting a schedule over several calls,
  * gives each pair the same bytes.  The order of the matches WITHIN a pair does matter: the sample
- * indices address it.  No refit on the inliers, no homography / degeneracy model selection, no
- * guided matching.  One launch enqueued on `stream`: no workspace, no allocation, no
+ * indices address it.  No refit on the inliers, no guided matching; the homography test that
+ * tells a planar or rotation-only pair apart is sfm_homography_matches_dev (below).  One launch enqueued on `stream`: no workspace, no allocation, no
  * synchronisation, no device read of host memory, so the call can be captured into a hipGraph.
  * SFM_EINVAL: nimg or cap < 1, P < 0, iters outside [0, 2^20], n_stop outside [0, 64], stop_ratio
  * null with n_stop > 0, min_inliers < 0, a null pointer (but every array indexed by p when
@@ -502,6 +502,93 @@ int32_t sfm_verify_matches_dev(sfm_ctx* ctx, const int32_t* xy, const int32_t* c
                                int32_t iters, double threshold, int32_t min_inliers, int64_t seed,
                                const double* stop_ratio, int32_t n_stop, uint8_t* keep, double* F, int32_t* stat,
                                void* stream);
+
+/* The two-view geometry record of a verified pair, first half: a homography RANSAC per pair, whose
+ * inlier count set against verify's tells a planar scene or a pure rotation (both pass the F test
+ * with a high count) from a general one.  COLMAP and OpenMVG keep such a record per verified pair;
+ * the reference has none.  The rule is the library's own, pinned to a numpy restatement
+ * (tests/two_view_ref.py).
+ * Inputs (device): xy, count, nimg, cap, pairs, P, matches, nmatch exactly as
+ * sfm_verify_matches_dev reads them; attempt [P] int32 (optional; NULL: every pair may be
+ * attempted), a pair with attempt[p] == 0 is skipped (pass a contiguous copy of column 3 of verify's stat).
+ * For pair p with slots (a, b) = pairs[p] and n = clamp(nmatch[p], 0, cap):
+ *  Attempted iff both slots lie in [0, nimg), a != b, n >= 4 and attempt allows it.  A pair that
+ *   is not attempted gets hstat = {-1, -1, 0, 0}, H all NaN, hkeep all 0.
+ *  Candidates: valid matches as in sfm_verify_matches_dev.  An invalid match is never an inlier; a
+ *   sample that contains one counts 0.
+ *  Samples: verify's counter stream generalised to sample size 4, under a key of its own.  With
+ *   mix64 and G as there, keyH = mix64(mix64(seed ^ 0x486F6D6F67726170) + ((a << 32) | b)); draw
+ *   k = 0..3 of sample it is r = mix64(keyH + (4 it + k + 1) G) >> 32, and the four indices are the
+ *   first four steps of the same Fisher-Yates over a virtual arange(n): j = k + ((r (n - k)) >> 32),
+ *   the k-th index is the value now at position j, then positions k and j are swapped.
+ *  Fit, float64 without contraction: Hartley normalisation over the four points of each image
+ *   (mean, mean distance, s = sqrt(2) / mean distance; the arithmetic of the 8-point fit over four
+ *   points); the 8 x 9 DLT system whose rows for point i = 0..3, in point order, are
+ *   [-x -y -1 0 0 0 x'x x'y x'] and [0 0 0 -x -y -1 y'x y'y y'] on the normalised (x, y) -> (x', y');
+ *   its null vector by the elimination of the 8-point fit (partial pivoting, the last free column
+ *   set to 1); H = T2^-1 Hn T1 with T = [[s, 0, -s cx], [0, s, -s cy], [0, 0, 1]], written out as
+ *   M = Hn T1 (M[r][0] = Hn[r][0] s1, M[r][1] = Hn[r][1] s1,
+ *   M[r][2] = (Hn[r][0] (-s1 c1x) + Hn[r][1] (-s1 c1y)) + Hn[r][2]), then H[0] = M[0] (1 / s2) + c2x M[2],
+ *   H[1] = M[1] (1 / s2) + c2y M[2], H[2] = M[2] by rows.  No unit norm, no degeneracy test of the
+ *   sample: a collinear sample simply scores low.
+ *  Inlier test, no division and no square root: with (u, v, w) = H (x1, y1, 1), each as
+ *   (H[3r] x1 + H[3r+1] y1) + H[3r+2], the forward transfer is ok iff
+ *   (x2 w - u)^2 + (y2 w - v)^2 < thr2 (w w), thr2 = threshold^2.  The backward transfer is the
+ *   same test with adj(H) (the transposed cofactors, each entry one difference of two products)
+ *   on (x2, y2, 1) against (x1, y1).  A match is an inlier iff both hold.  Any NaN compares false,
+ *   w == 0 admits nothing (also at threshold = inf), and a threshold that is <= 0 or NaN admits
+ *   nothing.
+ *  Rounds of 256, early stop against the caller's stop_ratio (a HOST array, copied into the
+ *   kernel's arguments; for this sample size pose.ransac_stop_ratios(c, r, 4)), winner (largest
+ *   count, lowest sample): as sfm_verify_matches_dev.
+ * Outputs (device): H [P][9] float64 row-major, the winner's — the one that produced the count;
+ * NaN when no sample had an inlier (scale and sign unspecified); hkeep [P][cap] uint8 (optional):
+ * the winner's inlier mask when its count is > 0, else 0, every one of the cap bytes written;
+ * hstat [P][4] int32 = best count, winning sample, samples evaluated, 0.  iters == 0: every
+ * attempted pair gets {0, -1, 0, 0}.
+ * Two runs write the same bytes; permuting the pairs or splitting the schedule gives each pair
+ * the same bytes.  One launch enqueued on `stream`: no workspace, no allocation, no
+ * synchronisation, no device read of host memory, so the call can be captured into a hipGraph.
+ * SFM_EINVAL: nimg or cap < 1, P < 0, iters outside [0, 2^20], n_stop outside [0, 64], stop_ratio
+ * null with n_stop > 0, a null pointer (but attempt and hkeep; every array indexed by p when
+ * P == 0). */
+int32_t sfm_homography_matches_dev(sfm_ctx* ctx, const int32_t* xy, const int32_t* count, int32_t nimg, int64_t cap,
+                                   const int32_t* pairs, int32_t P, const int32_t* matches, const int32_t* nmatch,
+                                   const int32_t* attempt, int32_t iters, double threshold, int64_t seed,
+                                   const double* stop_ratio, int32_t n_stop, double* H, uint8_t* hkeep,
+                                   int32_t* hstat, void* stream);
+
+/* The two-view geometry record, second half: the relative pose (R, t) of each verified pair out
+ * of verify's F and the intrinsics, chosen by a cheirality count, and the number of its points
+ * with enough parallax.  No RANSAC.  The rule is the library's own (tests/two_view_ref.py).
+ * Inputs (device): the slot table, pairs, matches, nmatch as above; keep [P][cap] uint8 and
+ * F [P][9] as sfm_verify_matches_dev wrote them; K [nimg][9] float64 row-major, one intrinsic
+ * matrix per slot; attempt [P] int32 (optional, as above); cos2_min, the squared cosine of the
+ * minimum parallax angle, a host value.
+ * For pair p with slots (a, b):
+ *  Attempted iff both slots lie in [0, nimg), a != b, attempt allows it and all nine entries of
+ *   F[p] are finite.  Otherwise pstat = {-1, -1, 0, 0} and pose is all NaN.
+ *  Points: the matches m < n with keep[p][m] != 0 and both rows valid; n_points is their number.
+ *  Candidates: E = K[b]^T F K[a] and the four poses (R1, T), (R1, -T), (R2, T), (R2, -T) of
+ *   sfm_ransac_camera_motion_dev, the same arithmetic, numbered 0..3 in this order.
+ *  Cheirality count: P1 = K[a] [I | 0], P2 = K[b] [R | t]; X by the linear triangulation of
+ *   sfm_triangulate_dev on raw pixels.  A point is in front iff X_z >= 1e-6 and
+ *   (R X + t)_z >= 1e-6, the latter as (R[6] X_x + R[7] X_y + R[8] X_z) + t_z; a NaN is not in
+ *   front.  The winner is the candidate with the largest count, the lowest number on a tie; a
+ *   largest count of 0 gives pose NaN, candidate -1 and n_front 0.
+ *  Parallax, over the winner's front points: C = -R^T t, e = X - C, d = X . e (each dot product
+ *   summed left to right).  The point is wide iff d <= 0 or d^2 < (cos2_min |X|^2) |e|^2: the angle
+ *   at X between the rays to the two centres is at least the minimum.  No sqrt, no acos.
+ * Outputs (device): pose [P][12] float64, R row-major then t (|t| = 1); pstat [P][4] int32 =
+ * n_front, candidate, n_wide, n_points.
+ * Counts are integers: two runs, any order of the pairs and any split of the schedule write the
+ * same bytes.  One launch enqueued on `stream`, nothing allocated, nothing synchronised,
+ * capturable into a hipGraph.  SFM_EINVAL: nimg or cap < 1, P < 0, a null pointer (but attempt;
+ * every array indexed by p when P == 0). */
+int32_t sfm_two_view_pose_dev(sfm_ctx* ctx, const int32_t* xy, const int32_t* count, int32_t nimg, int64_t cap,
+                              const int32_t* pairs, int32_t P, const int32_t* matches, const int32_t* nmatch,
+                              const uint8_t* keep, const double* F, const double* K, const int32_t* attempt,
+                              double cos2_min, double* pose, int32_t* pstat, void* stream);
 
 /* Each track's 3-D point from all its views: CameraPose.triangulate_point (SFM.py:241-246)
  * extended from 2 to V views.  track_offsets / obs_slot / obs_row: the CSR of

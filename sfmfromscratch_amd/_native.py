@@ -84,6 +84,14 @@ SIGNATURES = {
     "sfm_verify_matches_dev": (ctypes.c_int32, [_vp, _vp, _vp, ctypes.c_int32, ctypes.c_int64, _vp, ctypes.c_int32,
                                                 _vp, _vp, ctypes.c_int32, ctypes.c_double, ctypes.c_int32,
                                                 ctypes.c_int64, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp]),
+    # ctx, xy, count, nimg, cap, pairs, P, matches, nmatch, attempt, iters, threshold, seed,
+    # stop_ratio (host), n_stop, H, hkeep, hstat, stream
+    "sfm_homography_matches_dev": (ctypes.c_int32, [_vp, _vp, _vp, ctypes.c_int32, ctypes.c_int64, _vp,
+                                                    ctypes.c_int32, _vp, _vp, _vp, ctypes.c_int32, ctypes.c_double,
+                                                    ctypes.c_int64, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp]),
+    # ctx, xy, count, nimg, cap, pairs, P, matches, nmatch, keep, F, K, attempt, cos2_min, pose, pstat, stream
+    "sfm_two_view_pose_dev": (ctypes.c_int32, [_vp, _vp, _vp, ctypes.c_int32, ctypes.c_int64, _vp, ctypes.c_int32,
+                                               _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _vp, _vp, _vp]),
     "sfm_ingest_rgb_dev": (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                             ctypes.c_int32, ctypes.c_int32, _vp, _vp]),
     "sfm_extract_batch_dev": (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp,
@@ -574,6 +582,50 @@ class Context:
                 tp(keep, "uint8", P * cap, "keep", optional=P == 0), tp(F, "float64", 9 * P, "F", optional=P == 0),
                 tp(stat, "int32", 4 * P, "stat", optional=P == 0)]
         check(self.lib.sfm_verify_matches_dev(self.handle, *args, stream or None), self.handle)
+
+    def _pair_table_args(self, xy, count, pairs, matches, nmatch):
+        """The leading arguments the per-pair calls share -> (args, nimg, cap, P)."""
+        if len(getattr(xy, "shape", ())) != 3 or xy.shape[2] != 2:
+            raise ValueError("xy must be [nimg, cap, 2]")
+        nimg, cap = int(xy.shape[0]), int(xy.shape[1])
+        P = int(pairs.shape[0]) if pairs is not None and hasattr(pairs, "shape") and len(pairs.shape) == 2 else 0
+        if pairs is not None and tuple(getattr(pairs, "shape", ())) != (P, 2):
+            raise ValueError("pairs must be [P, 2]")
+        tp = self._tensor_ptr
+        args = [tp(xy, "int32", nimg * cap * 2, "xy"), tp(count, "int32", nimg, "count"), nimg, cap,
+                tp(pairs, "int32", 2 * P, "pairs", optional=P == 0), P,
+                tp(matches, "int32", 2 * P * cap, "matches", optional=P == 0),
+                tp(nmatch, "int32", P, "nmatch", optional=P == 0)]
+        return args, nimg, cap, P
+
+    def homography_matches_dev(self, xy, count, pairs, matches, nmatch, attempt, iters: int, threshold: float,
+                               seed: int, stop_ratio, H, hkeep, hstat, stream: int = 0):
+        """sfm_homography_matches_dev over device tensors (include/sfmfeat.h has the rule): the table
+        arguments of verify_matches_dev; attempt [P] int32 or None; stop_ratio a host sequence of at
+        most 64 floats (None or empty: fixed iterations); outputs H [P, 9] float64, hkeep [P, cap] uint8
+        or None, hstat [P, 4] int32."""
+        args, nimg, cap, P = self._pair_table_args(xy, count, pairs, matches, nmatch)
+        sr = np.ascontiguousarray(np.asarray([] if stop_ratio is None else stop_ratio, np.float64).reshape(-1))
+        tp = self._tensor_ptr
+        args += [tp(attempt, "int32", P, "attempt", optional=True), int(iters), float(threshold), int(seed),
+                 sr.ctypes.data if len(sr) else None, len(sr), tp(H, "float64", 9 * P, "H", optional=P == 0),
+                 tp(hkeep, "uint8", P * cap, "hkeep", optional=True),
+                 tp(hstat, "int32", 4 * P, "hstat", optional=P == 0)]
+        check(self.lib.sfm_homography_matches_dev(self.handle, *args, stream or None), self.handle)
+
+    def two_view_pose_dev(self, xy, count, pairs, matches, nmatch, keep, F, K, attempt, cos2_min: float, pose, pstat,
+                          stream: int = 0):
+        """sfm_two_view_pose_dev over device tensors (include/sfmfeat.h has the rule): the table
+        arguments of verify_matches_dev; keep [P, cap] uint8 and F [P, 9] float64 as verify wrote them;
+        K [nimg, 9] (or [nimg, 3, 3]) float64; attempt [P] int32 or None; outputs pose [P, 12] float64,
+        pstat [P, 4] int32."""
+        args, nimg, cap, P = self._pair_table_args(xy, count, pairs, matches, nmatch)
+        tp = self._tensor_ptr
+        args += [tp(keep, "uint8", P * cap, "keep", optional=P == 0), tp(F, "float64", 9 * P, "F", optional=P == 0),
+                 tp(K, "float64", 9 * nimg, "K"), tp(attempt, "int32", P, "attempt", optional=True), float(cos2_min),
+                 tp(pose, "float64", 12 * P, "pose", optional=P == 0),
+                 tp(pstat, "int32", 4 * P, "pstat", optional=P == 0)]
+        check(self.lib.sfm_two_view_pose_dev(self.handle, *args, stream or None), self.handle)
 
     def triangulate_tracks_dev(self, track_offsets, obs_slot, obs_row, n_tracks: int, n_obs: int, xy, P, cam_valid,
                                X, out_views, stream: int = 0):

@@ -220,6 +220,20 @@ void launch_verify(const int32_t* xy, const int32_t* count, int nimg, int64_t ca
                    const int32_t* matches, const int32_t* nmatch, int iters, double thr, int min_inliers,
                    uint64_t seed, const VerifyStop& stop, uint8_t* keep, double* F, int32_t* stat, hipStream_t st);
 
+// twoview.hip: sfm_homography_matches_dev and sfm_two_view_pose_dev (include/sfmfeat.h has the
+// rules).  The homography RANSAC shares verify's rounds and stop table; its sample stream is
+// verify's with this constant xor-ed into the seed ("Homograp" in ASCII), so the two never draw
+// the same numbers for one (seed, a, b).
+constexpr uint64_t kHomographySeedXor = 0x486F6D6F67726170ull;
+void launch_homography(const int32_t* xy, const int32_t* count, int nimg, int64_t cap, const int32_t* pairs, int P,
+                       const int32_t* matches, const int32_t* nmatch, const int32_t* attempt, int iters, double thr,
+                       uint64_t seed, const VerifyStop& stop, double* H, uint8_t* hkeep, int32_t* hstat,
+                       hipStream_t st);
+void launch_two_view_pose(const int32_t* xy, const int32_t* count, int nimg, int64_t cap, const int32_t* pairs, int P,
+                          const int32_t* matches, const int32_t* nmatch, const uint8_t* keep, const double* F,
+                          const double* K, const int32_t* attempt, double cos2_min, double* pose, int32_t* pstat,
+                          hipStream_t st);
+
 // pose.hip: CameraPose.ransac_camera_motion (SFM.py:38-124) on top of the RANSAC launches, and
 // triangulate_point / triangulate_points (SFM.py:239-253, 292-305).  Kc [P][2][9] (K1, K2),
 // base [P][12] (R_base, T_base), cand [P][iters][21] (R1, R2, T), cand_idx [P][iters] (the

@@ -10,29 +10,35 @@
 
 namespace sfm {
 
-SFM_DEV void normalise8(const double (&x)[8], const double (&y)[8], double (&nx)[8], double (&ny)[8], double& s,
-                        double& cx, double& cy) {
-  // CameraPose.normalize_points (SFM.py:164-178)
+// CameraPose.normalize_points (SFM.py:164-178) over the N points of a sample, sums in index order
+template <int N>
+SFM_DEV void normalise_sample(const double (&x)[N], const double (&y)[N], double (&nx)[N], double (&ny)[N], double& s,
+                              double& cx, double& cy) {
   double mx = 0.0, my = 0.0;
 #pragma unroll
-  for (int i = 0; i < 8; ++i) {
+  for (int i = 0; i < N; ++i) {
     mx += x[i];
     my += y[i];
   }
-  mx /= 8.0;
-  my /= 8.0;
+  mx /= (double)N;
+  my /= (double)N;
   double md = 0.0;
 #pragma unroll
-  for (int i = 0; i < 8; ++i) md += sqrt((x[i] - mx) * (x[i] - mx) + (y[i] - my) * (y[i] - my));
-  md /= 8.0;
+  for (int i = 0; i < N; ++i) md += sqrt((x[i] - mx) * (x[i] - mx) + (y[i] - my) * (y[i] - my));
+  md /= (double)N;
   s = sqrt(2.0) / md;
   cx = mx;
   cy = my;
 #pragma unroll
-  for (int i = 0; i < 8; ++i) {
+  for (int i = 0; i < N; ++i) {
     nx[i] = s * x[i] + (-s * mx);
     ny[i] = s * y[i] + (-s * my);
   }
+}
+
+SFM_DEV void normalise8(const double (&x)[8], const double (&y)[8], double (&nx)[8], double (&ny)[8], double& s,
+                        double& cx, double& cy) {
+  normalise_sample<8>(x, y, nx, ny, s, cx, cy);
 }
 
 // A null vector of the 8 x 9 system (rows [x1x2, y1x2, x2, x1y2, y1y2, y2, x1, y1, 1]): the last

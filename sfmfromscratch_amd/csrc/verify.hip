@@ -29,69 +29,13 @@
 
 #include "kernels.h"
 #include "ransac_dev.h"
+#include "verify_dev.h"  // mix64, pair_key, sample_indices, load_corr, stage
 
 namespace sfm {
 
 namespace {
 
-constexpr int kVerifyThreads = kVerifyRound;  // one thread per sample of a round
-constexpr int kVerifySweep = 4;               // points in flight per thread in the sweep
-
-SFM_DEV uint64_t mix64(uint64_t z) {  // the splitmix64 finaliser
-  z ^= z >> 30;
-  z *= 0xBF58476D1CE4E5B9ull;
-  z ^= z >> 27;
-  z *= 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return z;
-}
-
-// The eight indices of sample `it`: a Fisher-Yates over a virtual arange(n) of which only the
-// swapped positions are recorded (draw k writes position j_k; position k is never read again).
-// Every index is compile-time, so the records stay in registers.
-SFM_DEV void sample8(uint64_t key, int it, int n, int (&idx)[8]) {
-  int pos[8], val[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const uint64_t r = mix64(key + (uint64_t)(8 * (int64_t)it + k + 1) * 0x9E3779B97F4A7C15ull) >> 32;
-    const int j = k + (int)((r * (uint64_t)(n - k)) >> 32);
-    int vj = j, vk = k;  // the values now at positions j and k: the latest record of each
-#pragma unroll
-    for (int i = 0; i < k; ++i) {
-      vj = pos[i] == j ? val[i] : vj;
-      vk = pos[i] == k ? val[i] : vk;
-    }
-    idx[k] = vj;
-    pos[k] = j;
-    val[k] = vk;
-  }
-}
-
-struct Corr {
-  double x1, y1, x2, y2;
-};
-
-// correspondence m of the pair: NaN when a row lies outside [0, count) of its slot
-SFM_DEV Corr load_corr(const int2* __restrict__ mt, const int2* __restrict__ xa, const int2* __restrict__ xb, int ca,
-                       int cb, int m) {
-  const int2 rr = mt[m];
-  if (rr.x < 0 || rr.x >= ca || rr.y < 0 || rr.y >= cb) {
-    const double q = __builtin_nan("");
-    return {q, q, q, q};
-  }
-  const int2 u = xa[rr.x], v = xb[rr.y];
-  return {(double)u.x, (double)u.y, (double)v.x, (double)v.y};
-}
-
-SFM_DEV void stage(double* s_pd, const int2* mt, const int2* xa, const int2* xb, int ca, int cb, int i0, int m) {
-  for (int i = threadIdx.x; i < m; i += kVerifyThreads) {
-    const Corr q = load_corr(mt, xa, xb, ca, cb, i0 + i);
-    s_pd[4 * i + 0] = q.x1;
-    s_pd[4 * i + 1] = q.y1;
-    s_pd[4 * i + 2] = q.x2;
-    s_pd[4 * i + 3] = q.y2;
-  }
-}
+constexpr int kVerifySweep = 4;  // points in flight per thread in the sweep
 
 // The inliers of f among m staged points.  Two waves per SIMD hide little latency, so four points
 // go through the test together: their LDS reads first, then their terms, then their decisions.
@@ -149,7 +93,7 @@ k_verify(const int32_t* __restrict__ xy, const int32_t* __restrict__ count, int 
   const int2* mt = reinterpret_cast<const int2*>(matches) + (int64_t)p * cap;
   const int2* xa = reinterpret_cast<const int2*>(xy) + (int64_t)a * cap;
   const int2* xb = reinterpret_cast<const int2*>(xy) + (int64_t)b * cap;
-  const uint64_t key = mix64(mix64(seed) + (((uint64_t)(uint32_t)a << 32) | (uint64_t)(uint32_t)b));
+  const uint64_t key = pair_key(seed, a, b);
   const EpiThr t = epi_thr(thr);
   const bool multi = n > kRansacChunk;
   if (!multi) {
@@ -167,7 +111,7 @@ k_verify(const int32_t* __restrict__ xy, const int32_t* __restrict__ count, int 
     for (int k = 0; k < 9; ++k) f[k] = qnan;
     if (in_round) {
       int idx[8];
-      sample8(key, it, n, idx);
+      sample_indices<8>(key, it, n, idx);
       double x1[8], y1[8], x2[8], y2[8];
 #pragma unroll
       for (int k = 0; k < 8; ++k) {

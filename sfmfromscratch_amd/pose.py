@@ -38,15 +38,19 @@ def calculate_num_ransac_iterations(prob_success: float, sample_size: int, ind_p
     return int(num_samples)
 
 
-def ransac_stop_ratios(confidence: float, rounds: int) -> np.ndarray:
+def ransac_stop_ratios(confidence: float, rounds: int, sample_size: int = 8) -> np.ndarray:
     """The early-stop table of sequence.verify_matches (sfm_verify_matches_dev's stop_ratio): entry
     r - 1, r = 1..rounds, is (1 - (1 - confidence)^(1 / (256 r)))^(1 / 8), the inlier ratio w at which
     256 r eight-point samples contain an all-inlier one with probability `confidence`
-    (1 - (1 - w^8)^(256 r) = confidence).  Pure numpy, float64; strictly decreasing in r."""
+    (1 - (1 - w^8)^(256 r) = confidence).  sample_size=4 gives the table of
+    sequence.two_view_geometry's homography RANSAC (w^4 in place of w^8).  Pure numpy, float64;
+    strictly decreasing in r."""
     if not 0.0 < confidence < 1.0:
         raise ValueError("confidence must lie in (0, 1)")
+    if int(sample_size) < 1:
+        raise ValueError("sample_size must be >= 1")
     r = np.arange(1, int(rounds) + 1, dtype=np.float64)
-    return (-np.expm1(np.log1p(-np.float64(confidence)) / (256.0 * r))) ** 0.125
+    return (-np.expm1(np.log1p(-np.float64(confidence)) / (256.0 * r))) ** (1.0 / int(sample_size))
 
 
 def sample_indices(n: int, iters: int, seed: int = 5) -> np.ndarray:

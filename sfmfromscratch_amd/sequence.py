@@ -573,3 +573,151 @@ def verify_matches(cache, pairs, matches, threshold: float = 1.0, max_iterations
         ctx.verify_matches_dev(slots.xy, slots.count, pt, mm, nm, iters, float(threshold), int(min_inliers), int(seed),
                                stop, keep, F, stat, stream)
     return Verified(keep, F, stat, pt, mm, cc, nm)
+
+
+# ---------------- two-view geometry (twoview.hip) ----------------
+
+class TwoView:
+    """The two-view geometry record of every pair of a schedule, as sfm_homography_matches_dev and
+    sfm_two_view_pose_dev leave it (include/sfmfeat.h has both rules).  The device tensors stay
+    resident: `H_dev` [P, 9] float64, `hstat_dev` [P, 4] int32, `hkeep_dev` [P, cap] uint8 (the
+    homography's inlier mask), `pose_dev` [P, 12] float64 (R row-major, then t), `pstat_dev` [P, 4]
+    int32.  The numpy properties copy on first use, which synchronises."""
+
+    def __init__(self, H, hstat, hkeep, pose, pstat, verified_stat, planar_ratio):
+        self.H_dev, self.hstat_dev, self.hkeep_dev, self.pose_dev, self.pstat_dev = H, hstat, hkeep, pose, pstat
+        self._vstat, self.planar_ratio = verified_stat, float(planar_ratio)
+        self._host = {}
+
+    def _np(self, key, t):
+        if key not in self._host:
+            self._host[key] = t.cpu().numpy()
+        return self._host[key]
+
+    @property
+    def H(self) -> np.ndarray:
+        """[P, 3, 3] float64: the homography RANSAC's winner (NaN where it had no inlier)."""
+        return self._np("H", self.H_dev).reshape(-1, 3, 3)
+
+    @property
+    def n_homography(self) -> np.ndarray:
+        """The homography's inlier count per pair (-1: not attempted)."""
+        return self._np("hstat", self.hstat_dev)[:, 0]
+
+    @property
+    def R(self) -> np.ndarray:
+        """[P, 3, 3]: the second camera's rotation relative to the first (NaN without a pose)."""
+        return self._np("pose", self.pose_dev)[:, :9].reshape(-1, 3, 3)
+
+    @property
+    def t(self) -> np.ndarray:
+        """[P, 3]: the unit translation that goes with R."""
+        return self._np("pose", self.pose_dev)[:, 9:]
+
+    @property
+    def n_front(self) -> np.ndarray:
+        """Inliers in front of both cameras under the chosen pose (-1: not attempted)."""
+        return self._np("pstat", self.pstat_dev)[:, 0]
+
+    @property
+    def n_wide(self) -> np.ndarray:
+        """Those of them whose parallax reaches min_parallax_deg."""
+        return self._np("pstat", self.pstat_dev)[:, 2]
+
+    @property
+    def config(self) -> np.ndarray:
+        """int8 per pair: 0 not verified; 1 general; 2 planar or panoramic (the homography explains
+        at least planar_ratio of verify's inliers); 3 verified, but no candidate pose has a point in
+        front of both cameras."""
+        if "config" not in self._host:
+            vs = self._np("vstat", self._vstat)
+            out = np.zeros(len(vs), np.int8)
+            ok = vs[:, 3] != 0
+            planar = ok & (self.n_homography >= self.planar_ratio * vs[:, 0])
+            out[ok] = 1
+            out[ok & ~planar & (self._np("pstat", self.pstat_dev)[:, 1] < 0)] = 3
+            out[planar] = 2
+            self._host["config"] = out
+        return self._host["config"]
+
+    def initial_pair(self) -> int:
+        """The index of the general pair with the most wide points, the lowest index on a tie; -1 if
+        the schedule has no general pair."""
+        general = np.flatnonzero(self.config == 1)
+        if len(general) == 0:
+            return -1
+        return int(general[np.argmax(self.n_wide[general])])   # argmax: the first of the largest
+
+
+def two_view_geometry(cache, pairs, matches, verified, K, h_threshold: float = 2.0, h_iterations: int | None = None,
+                      confidence: float | None = 0.98, planar_ratio: float = 0.8, min_parallax_deg: float = 2.0,
+                      seed: int = 5) -> TwoView:
+    """The two-view geometry record of every verified pair of a schedule, on the device between
+    verify_matches and build_tracks / triangulate_tracks: a homography RANSAC (symmetric transfer
+    error < `h_threshold` pixels) whose inlier count, set against verify's, marks planar and
+    rotation-only pairs; the relative pose (R, t) out of verify's F and the intrinsics, chosen by a
+    cheirality count; and the number of inliers whose parallax reaches `min_parallax_deg`
+    (include/sfmfeat.h sfm_homography_matches_dev and sfm_two_view_pose_dev have the rules).
+    `TwoView.initial_pair()` names the pair to start a reconstruction from.
+
+    cache, pairs, matches: as verify_matches took them.  verified: its result.  K: [3, 3], or
+    [nimg, 3, 3] with one matrix per slot; a host array is uploaded, a device tensor used in place.
+    h_iterations=None is pose.calculate_num_ransac_iterations(0.98, 4, 0.4) = 150.  confidence: the
+    early stop of verify_matches, for four-point samples (None or 0: off).  planar_ratio=0.8 is
+    COLMAP's max_H_inlier_ratio; the other defaults are this library's own: h_threshold is 2.0 px
+    because keypoints are integer pixels in both images (at 1.0 px planar and rotation-only scenes
+    land on either side of 0.8).  Only pairs that verify_matches verified are
+    attempted.  Enqueued on torch's current stream; nothing synchronises until a host property of
+    the result is read."""
+    import math
+    import torch
+    from . import _abi, pose
+    from ._native import context_for
+    slots = getattr(cache, "slots", cache)
+    dev = slots.xy.device
+    nimg, cap = int(slots.count.numel()), int(slots.xy.shape[1])
+    extractor = getattr(cache, "extractor", None)
+    ctx = extractor.ctx if extractor is not None else \
+        context_for(_abi.params_from_dict({}, _abi.SFM_MODE_NAIVE), dev.index or 0)
+    if isinstance(pairs, torch.Tensor):
+        pt = pairs.to(device=dev, dtype=torch.int32).reshape(-1, 2).contiguous()
+    else:
+        pt = torch.from_numpy(np.ascontiguousarray(np.asarray(pairs).reshape(-1, 2), np.int32)).to(dev)
+    P = int(pt.shape[0])
+    if tuple(verified.stat_dev.shape) != (P, 4) or tuple(verified.keep_dev.shape) != (P, cap):
+        raise ValueError(f"two_view_geometry: verified must be verify_matches' result for these {P} pairs")
+    iters = pose.calculate_num_ransac_iterations(0.98, 4, 0.4) if h_iterations is None else int(h_iterations)
+    stop = None
+    if confidence:
+        stop = pose.ransac_stop_ratios(float(confidence), min(64, (max(iters, 0) + 255) // 256), 4)
+    if not 0.0 <= float(min_parallax_deg) <= 90.0:
+        raise ValueError("two_view_geometry: min_parallax_deg must lie in [0, 90]")
+    cos2_min = math.cos(math.radians(float(min_parallax_deg))) ** 2
+    with torch.cuda.device(dev):
+        if isinstance(K, torch.Tensor):
+            Kt = K.to(device=dev, dtype=torch.float64)
+        else:
+            Kt = torch.from_numpy(np.ascontiguousarray(np.asarray(K, np.float64))).to(dev)
+        if tuple(Kt.shape) == (3, 3):
+            Kt = Kt.reshape(1, 9).expand(nimg, 9)
+        elif tuple(Kt.shape) != (nimg, 3, 3):
+            raise ValueError(f"two_view_geometry: K must be [3, 3] or [{nimg}, 3, 3]")
+        Kt = Kt.reshape(nimg, 9).contiguous()
+        if len(matches) == 3 and isinstance(matches[0], torch.Tensor):
+            mm, nm = matches[0], matches[2]
+            if mm.dim() != 3 or tuple(mm.shape[1:]) != (cap, 2) or int(mm.shape[0]) < P:
+                raise ValueError(f"two_view_geometry: matches must be [P, {cap}, 2] for the table's capacity")
+        else:
+            mm, nm, _ = _padded_matches(torch, matches, None, P, cap, dev, who="two_view_geometry")
+        attempt = verified.stat_dev[:, 3].contiguous()
+        H = torch.empty((P, 9), dtype=torch.float64, device=dev)
+        hkeep = torch.empty((P, cap), dtype=torch.uint8, device=dev)
+        hstat = torch.empty((P, 4), dtype=torch.int32, device=dev)
+        rt = torch.empty((P, 12), dtype=torch.float64, device=dev)
+        pstat = torch.empty((P, 4), dtype=torch.int32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        ctx.homography_matches_dev(slots.xy, slots.count, pt, mm, nm, attempt, iters, float(h_threshold), int(seed),
+                                   stop, H, hkeep, hstat, stream)
+        ctx.two_view_pose_dev(slots.xy, slots.count, pt, mm, nm, verified.keep_dev, verified.F_dev, Kt, attempt,
+                              cos2_min, rt, pstat, stream)
+    return TwoView(H, hstat, hkeep, rt, pstat, verified.stat_dev, planar_ratio)
