@@ -609,6 +609,55 @@ int32_t sfm_triangulate_tracks_dev(sfm_ctx* ctx, const int32_t* track_offsets, c
                                    int32_t nimg, int64_t cap, const double* P, const uint8_t* cam_valid,
                                    int32_t n_cam, double* X, int32_t* out_views, void* stream);
 
+/* Resection from tracks: the pose of every frame of a slot table that has none yet, from the
+ * 2D-3D links its feature tracks give it, all frames in one call.  The step between the initial
+ * pair (sfm_two_view_pose_dev) and the triangulation of the model (sfm_triangulate_tracks_dev);
+ * the rule is the library's own (tests/resect_ref.py).
+ * Inputs (device): xy [nimg][cap][2] int32 and count [nimg] of the slot table; node_track
+ * [nimg][cap] int32 as sfm_build_tracks_dev wrote it; X [n_tracks][3] float64 as
+ * sfm_triangulate_tracks_dev wrote it (NaN: no point; may be null when n_tracks == 0); K [nimg][9]
+ * float64 row-major, one intrinsic matrix per slot; attempt [nimg] uint8 (optional; null: every
+ * slot, else only the slots with a non-zero entry).  Host values: n_tracks, iters, threshold,
+ * min_inliers, seed, max_refine_iter.
+ * For slot s:
+ *  Links: c = clamp(count[s], 0, cap); row r < c is a link iff t = node_track[s][r] lies in
+ *   [0, n_tracks) and all three of X[t] are finite.  The links are taken in ascending r; link i is
+ *   the correspondence (X[t_i], (double)xy[s][r_i]).  n_links is written for every slot.
+ *  Attempted iff attempt allows it, n_links >= 6 and K[s] is finite and upper triangular with a
+ *   non-zero diagonal.  Otherwise rstat = {-1, -1, 0, n_links, 0, -1, 0, 0}, pose and rcost are NaN,
+ *   the rkeep row is 0, the out_counts row 0 and the out_hyp row NaN.
+ *  Samples: the counter stream of sfm_verify_matches_dev at sample size 6 under a key of its own,
+ *   keyR = mix64(mix64(seed ^ 0x526573656374696F) + (uint64)(uint32)s); draw k = 0..5 of sample it
+ *   is mix64(keyR + (6 it + k + 1) G) >> 32 with G = 0x9E3779B97F4A7C15, and the indices are the
+ *   first six steps of the Fisher-Yates shuffle of arange(n_links) those draws give.  The indices
+ *   address the link list, not the rows.  The stream is a function of (seed, s, it) only.
+ *  Hypothesis, count, refinement: steps 2, 3 and 5 of sfm_pnp_ransac_dev over the links, the same
+ *   arithmetic in the same order.  Fixed iters: no rounds, no early stop.
+ *  Winner: the lowest sample with the largest count (sample -1 and count 0 when iters == 0).  The
+ *   slot is posed iff that count is > 0 and >= min_inliers; otherwise pose and rcost are NaN, the
+ *   rkeep row is 0 and rstat[4..7] = {0, -1, 0, 0}.  The refinement runs over the winner's inliers
+ *   in link order; the inliers are not re-scored.
+ * Outputs (device): pose [nimg][12] float64, R row-major then t; rstat [nimg][8] int32 = best
+ * count, winning sample, samples evaluated, n_links, posed (0 / 1), LM status, accepted steps, LM
+ * iterations; rcost [nimg][2] the sum of squared residuals over the inliers at the winning
+ * hypothesis and at the returned pose; rkeep [nimg][cap] uint8 (optional), 1 exactly at the rows
+ * that are links and inliers of a posed winner, every byte written; out_counts [nimg][iters] int32
+ * and out_hyp [nimg][iters][12] float64 (optional) every sample's count and (R, t).
+ * Two runs write the same bytes, and a slot gets the same bytes (those of its pose included)
+ * whatever attempt says about the other slots and however the table's slots are split over calls
+ * by attempt.  Five launches enqueued on `stream` whatever nimg is, nothing synchronised, no host
+ * memory read by the device.  The workspace (48 B per node of the table, 100 B per (slot, sample)
+ * where the caller passes no out_hyp / out_counts) grows on demand and is the only allocation:
+ * after a call of the same sizes the call can be captured into a hipGraph.  One call at a time
+ * per context.  SFM_EINVAL: nimg or cap < 1, n_tracks < 0, iters outside [0, 2^20], threshold not
+ * positive, min_inliers < 0, max_refine_iter outside [1, 2^24), a null pointer (but attempt,
+ * rkeep, out_counts, out_hyp, and X when n_tracks == 0), more than 2^30 nodes. */
+int32_t sfm_resect_tracks_dev(sfm_ctx* ctx, const int32_t* xy, const int32_t* count, int32_t nimg, int64_t cap,
+                              const int32_t* node_track, const double* X, int32_t n_tracks, const double* K,
+                              const uint8_t* attempt, int32_t iters, double threshold, int32_t min_inliers,
+                              int64_t seed, int32_t max_refine_iter, double* pose, int32_t* rstat, double* rcost,
+                              uint8_t* rkeep, int32_t* out_counts, double* out_hyp, void* stream);
+
 /* sfm_ingest_rgb for B frames: rgb [B][H][W][3] uint8 -> gray [B][H2][W2] float32 (device
  * pointers).  Enqueued on `stream`, not synchronised.  The tap tables and the temp image belong
  * to the context: one ingest call at a time per context, on one stream.  A call whose shape

@@ -92,6 +92,12 @@ SIGNATURES = {
     # ctx, xy, count, nimg, cap, pairs, P, matches, nmatch, keep, F, K, attempt, cos2_min, pose, pstat, stream
     "sfm_two_view_pose_dev": (ctypes.c_int32, [_vp, _vp, _vp, ctypes.c_int32, ctypes.c_int64, _vp, ctypes.c_int32,
                                                _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, _vp, _vp, _vp]),
+    # ctx, xy, count, nimg, cap, node_track, X, n_tracks, K, attempt, iters, threshold, min_inliers, seed,
+    # max_refine_iter, pose, rstat, rcost, rkeep, out_counts, out_hyp, stream
+    "sfm_resect_tracks_dev": (ctypes.c_int32, [_vp, _vp, _vp, ctypes.c_int32, ctypes.c_int64, _vp, _vp,
+                                               ctypes.c_int32, _vp, _vp, ctypes.c_int32, ctypes.c_double,
+                                               ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, _vp, _vp, _vp, _vp,
+                                               _vp, _vp, _vp]),
     "sfm_ingest_rgb_dev": (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                             ctypes.c_int32, ctypes.c_int32, _vp, _vp]),
     "sfm_extract_batch_dev": (ctypes.c_int32, [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp,
@@ -644,6 +650,28 @@ class Context:
                 tp(P, "float64", 12 * n_cam, "P"), tp(cam_valid, "uint8", n_cam, "cam_valid", optional=True), n_cam,
                 tp(X, "float64", 3 * T, "X", T == 0), tp(out_views, "int32", T, "out_views", T == 0)]
         check(self.lib.sfm_triangulate_tracks_dev(self.handle, *args, stream or None), self.handle)
+
+    def resect_tracks_dev(self, xy, count, node_track, X, n_tracks: int, K, attempt, iters: int, threshold: float,
+                          min_inliers: int, seed: int, max_refine_iter: int, pose, rstat, rcost, rkeep=None,
+                          out_counts=None, out_hyp=None, stream: int = 0):
+        """sfm_resect_tracks_dev over device tensors (include/sfmfeat.h has the rule): xy [nimg, cap, 2]
+        and count [nimg] int32 of the slot table, node_track [nimg, cap] int32, X [n_tracks, 3] float64
+        (None when n_tracks is 0), K [nimg, 9] (or [nimg, 3, 3]) float64, attempt [nimg] uint8 or None;
+        outputs pose [nimg, 12] float64, rstat [nimg, 8] int32, rcost [nimg, 2] float64 and, optional,
+        rkeep [nimg, cap] uint8, out_counts [nimg, iters] int32, out_hyp [nimg, iters, 12] float64."""
+        if len(getattr(xy, "shape", ())) != 3 or xy.shape[2] != 2:
+            raise ValueError("xy must be [nimg, cap, 2]")
+        nimg, cap, T, it = int(xy.shape[0]), int(xy.shape[1]), int(n_tracks), max(int(iters), 0)
+        tp = self._tensor_ptr
+        args = [tp(xy, "int32", nimg * cap * 2, "xy"), tp(count, "int32", nimg, "count"), nimg, cap,
+                tp(node_track, "int32", nimg * cap, "node_track"), tp(X, "float64", 3 * max(T, 0), "X", T <= 0), T,
+                tp(K, "float64", 9 * nimg, "K"), tp(attempt, "uint8", nimg, "attempt", optional=True), int(iters),
+                float(threshold), int(min_inliers), int(seed), int(max_refine_iter),
+                tp(pose, "float64", 12 * nimg, "pose"), tp(rstat, "int32", 8 * nimg, "rstat"),
+                tp(rcost, "float64", 2 * nimg, "rcost"), tp(rkeep, "uint8", nimg * cap, "rkeep", optional=True),
+                tp(out_counts, "int32", nimg * it, "out_counts", optional=True),
+                tp(out_hyp, "float64", 12 * nimg * it, "out_hyp", optional=True)]
+        check(self.lib.sfm_resect_tracks_dev(self.handle, *args, stream or None), self.handle)
 
 
 def copy_wg(dst_ptr: int, src_ptr: int, nbytes: int, workgroups: int, stream: int = 0):

@@ -11,6 +11,7 @@
 //                    are c->ransac's cache)
 //   api_ba.hip       c->ba (the plan's lists, the linearisation, the Schur system, the LM state)
 //   api_tracks.hip   c->tracks (the union-find, the (root, slot) table, the scans' tile sums)
+//   api_resect.hip   c->resect (each slot's compacted links, hypotheses, counts, the winners' inliers)
 //   api_profile.hip  c->prof   (stage events, Harris spans, the sfm_debug_* reads)
 #pragma once
 
@@ -204,6 +205,12 @@ struct TracksWs {
   DevBuf parent, size, state, tid, tmp, hash, bsum;
 };
 
+// Resection from tracks (sfm_resect_tracks_dev): kernels.h ResectProblem's workspace members.
+// Growing these is the call's only allocation.  One call at a time per context.
+struct ResectWs {
+  DevBuf Xl, xl, lrow, inl, n_links, go, n_inl, Rt0, hyp, counts;
+};
+
 struct sfm_ctx {
   CtxStreams s;  // (first: outlives the workspaces below)
   int device = 0;
@@ -227,6 +234,7 @@ struct sfm_ctx {
   PnpWs pnp;
   BaWs ba;
   TracksWs tracks;
+  ResectWs resect;
   // the workspaces free their buffers after this body, the streams and events go last
   ~sfm_ctx() {
     (void)hipSetDevice(device);

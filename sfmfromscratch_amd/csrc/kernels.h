@@ -234,6 +234,35 @@ void launch_two_view_pose(const int32_t* xy, const int32_t* count, int nimg, int
                           const double* K, const int32_t* attempt, double cos2_min, double* pose, int32_t* pstat,
                           hipStream_t st);
 
+// resect.hip: sfm_resect_tracks_dev (include/sfmfeat.h has the rule).  The sample stream is
+// verify's construction at sample size 6 with this constant xor-ed into the seed ("Resectio" in
+// ASCII) and the slot alone in the key.  Inputs and outputs as the C call names them; the rest is
+// workspace (api_resect.hip sizes it): Xl [nimg][cap][3], xl [nimg][cap][2] and lrow [nimg][cap]
+// the links of each slot in ascending row order, inl [nimg][cap] the winner's inliers as link
+// numbers, n_links, go (attempted), n_inl [nimg], Rt0 [nimg][12] the winning hypothesis,
+// hyp [nimg][iters][12] and counts [nimg][iters] (the caller's tables when it passes them).
+constexpr uint64_t kResectSeedXor = 0x526573656374696Full;
+struct ResectProblem {
+  const int32_t* xy;
+  const int32_t* count;
+  const int32_t* node_track;
+  const double* X;
+  const double* K;
+  const uint8_t* attempt;
+  int nimg, cap, n_tracks, iters, min_inliers, max_refine_iter;
+  double thr;
+  uint64_t seed;
+  double* pose;
+  int32_t* rstat;
+  double* rcost;
+  uint8_t* rkeep;
+  int32_t* out_counts;
+  double* out_hyp;
+  double *Xl, *xl, *hyp, *Rt0;
+  int32_t *lrow, *inl, *n_links, *go, *n_inl, *counts;
+};
+void launch_resect_tracks(const ResectProblem& q, hipStream_t st);
+
 // pose.hip: CameraPose.ransac_camera_motion (SFM.py:38-124) on top of the RANSAC launches, and
 // triangulate_point / triangulate_points (SFM.py:239-253, 292-305).  Kc [P][2][9] (K1, K2),
 // base [P][12] (R_base, T_base), cand [P][iters][21] (R1, R2, T), cand_idx [P][iters] (the

@@ -31,6 +31,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from .pose import PNP_THRESHOLD
 from .runner import convert_matches_to_coords, drop_opaque_alpha, load_image_u8
 
 
@@ -272,9 +273,10 @@ class Tracks:
     (`offsets_dev`, `obs_slot_dev`, `obs_row_dev`, `node_track_dev`, `xy`: the slot table's
     pixels); the numpy properties copy on first use, which synchronises."""
 
-    def __init__(self, offsets, obs_slot, obs_row, node_track, out_n, xy, min_len: int = 2):
+    def __init__(self, offsets, obs_slot, obs_row, node_track, out_n, xy, min_len: int = 2, count=None):
         self._offsets, self._obs_slot, self._obs_row = offsets, obs_slot, obs_row
         self.node_track_dev, self._out_n, self.xy, self.min_len = node_track, out_n, xy, int(min_len)
+        self.count_dev = count   # the slot table's count [nimg] (None: loaded tracks, every row counts)
         self._host = {}
 
     def _stat(self):
@@ -439,7 +441,7 @@ def build_tracks(cache, pairs, matches, keep=None, min_len: int = 2) -> Tracks:
         stream = torch.cuda.current_stream(dev).cuda_stream
         ctx.build_tracks_dev(slots.count, cap, pt, mm, nm, kk, int(min_len), offsets, obs_slot, obs_row, node_track,
                              out_n, stream)
-    return Tracks(offsets, obs_slot, obs_row, node_track, out_n, slots.xy, min_len)
+    return Tracks(offsets, obs_slot, obs_row, node_track, out_n, slots.xy, min_len, count=slots.count)
 
 
 # ---------------- geometric verification (verify.hip) ----------------
@@ -648,6 +650,22 @@ class TwoView:
             return -1
         return int(general[np.argmax(self.n_wide[general])])   # argmax: the first of the largest
 
+    def seed(self, pairs, index=None):
+        """(a, b, R [3, 3], t [3]) of pair `index` of the schedule `pairs` [P, 2] (None: initial_pair()),
+        the seed_pair of `reconstruct`.  ValueError when the schedule has no general pair, the index is
+        outside the schedule or that pair has no pose."""
+        pairs = np.asarray(pairs.cpu() if hasattr(pairs, "cpu") else pairs).reshape(-1, 2)
+        i = self.initial_pair() if index is None else int(index)
+        if len(pairs) != len(self.R):
+            raise ValueError(f"TwoView.seed: pairs has {len(pairs)} rows, the record {len(self.R)}: not its schedule")
+        if i < 0 or i >= len(pairs):
+            raise ValueError("TwoView.seed: the schedule has no such pair" if index is not None
+                             else "TwoView.seed: the schedule has no general pair to start from")
+        R, t = self.R[i], self.t[i]
+        if not (np.isfinite(R).all() and np.isfinite(t).all()):
+            raise ValueError(f"TwoView.seed: pair {i} has no relative pose")
+        return int(pairs[i, 0]), int(pairs[i, 1]), R.copy(), t.copy()
+
 
 def two_view_geometry(cache, pairs, matches, verified, K, h_threshold: float = 2.0, h_iterations: int | None = None,
                       confidence: float | None = 0.98, planar_ratio: float = 0.8, min_parallax_deg: float = 2.0,
@@ -721,3 +739,259 @@ def two_view_geometry(cache, pairs, matches, verified, K, h_threshold: float = 2
         ctx.two_view_pose_dev(slots.xy, slots.count, pt, mm, nm, verified.keep_dev, verified.F_dev, Kt, attempt,
                               cos2_min, rt, pstat, stream)
     return TwoView(H, hstat, hkeep, rt, pstat, verified.stat_dev, planar_ratio)
+
+
+# ---------------- resection from tracks and the reconstruction loop (resect.hip) ----------------
+
+RESECT_STATS = ("n_inliers", "best_iter", "samples", "n_links", "posed", "status", "iters", "lm_iters")
+
+
+class Resected:
+    """What sfm_resect_tracks_dev leaves for every slot of a table (include/sfmfeat.h has the rule).
+    The device tensors stay resident: `pose_dev` [nimg, 12] float64 (R row-major, then t; NaN
+    without a pose), `rstat_dev` [nimg, 8] int32, `cost_dev` [nimg, 2] float64, `keep_dev`
+    [nimg, cap] uint8 (1 at the rows that are links and inliers of a posed slot), `K_dev` [nimg, 9].
+    The numpy properties copy on first use, which synchronises."""
+
+    def __init__(self, pose, rstat, cost, keep, K):
+        self.pose_dev, self.rstat_dev, self.cost_dev, self.keep_dev, self.K_dev = pose, rstat, cost, keep, K
+        self._host = {}
+
+    def _np(self, key, t):
+        if key not in self._host:
+            self._host[key] = t.cpu().numpy()
+        return self._host[key]
+
+    @property
+    def stat(self) -> np.ndarray:
+        """[nimg, 8] int32: best count, winning sample, samples, n_links, posed, LM status, accepted
+        steps, LM iterations."""
+        return self._np("rstat", self.rstat_dev)
+
+    @property
+    def R(self) -> np.ndarray:
+        return self._np("pose", self.pose_dev)[:, :9].reshape(-1, 3, 3)
+
+    @property
+    def t(self) -> np.ndarray:
+        return self._np("pose", self.pose_dev)[:, 9:]
+
+    @property
+    def P(self) -> np.ndarray:
+        """[nimg, 3, 4]: K [R | t] (NaN without a pose)."""
+        K = self._np("K", self.K_dev).reshape(-1, 3, 3)
+        return K @ np.concatenate([self.R, self.t[:, :, None]], axis=2)
+
+    @property
+    def n_links(self) -> np.ndarray:
+        return self.stat[:, 3]
+
+    @property
+    def n_inliers(self) -> np.ndarray:
+        """The winner's inlier count per slot (-1: the slot was not attempted)."""
+        return self.stat[:, 0]
+
+    @property
+    def posed(self) -> np.ndarray:
+        return self.stat[:, 4] != 0
+
+    @property
+    def status(self) -> np.ndarray:
+        """The refinement's status per slot (pose.REFINE_STATUS; -1 without a pose)."""
+        return self.stat[:, 5]
+
+    @property
+    def cost(self) -> np.ndarray:
+        """[nimg, 2]: the sum of squared residuals over the inliers before and after the refinement."""
+        return self._np("cost", self.cost_dev)
+
+    def next_views(self) -> np.ndarray:
+        """The posed slots by descending n_inliers, the lowest slot first on a tie."""
+        s = np.flatnonzero(self.posed)
+        return s[np.argsort(-self.n_inliers[s].astype(np.int64), kind="stable")]
+
+
+def _slot_K(torch, K, nimg, dev, who):
+    """K [3, 3] or [nimg, 3, 3] -> [nimg, 9] float64 on the device; a host K is checked as
+    pose._pnp_inputs checks it (a device K is checked by the kernel, slot by slot)."""
+    if isinstance(K, torch.Tensor) and K.is_cuda:
+        Kt = K.to(device=dev, dtype=torch.float64)
+    else:
+        Kh = np.asarray(K.numpy() if isinstance(K, torch.Tensor) else K, np.float64)
+        if Kh.shape != (3, 3) and Kh.shape != (nimg, 3, 3):
+            raise ValueError(f"{who}: K must be [3, 3] or [{nimg}, 3, 3]")
+        Kf = Kh.reshape(-1, 9)
+        if not np.isfinite(Kf).all():
+            raise ValueError(f"{who}: K must be finite")
+        if (Kf[:, [3, 6, 7]] != 0).any() or (Kf[:, [0, 4, 8]] == 0).any():
+            raise ValueError(f"{who}: K must be upper triangular with a non-zero diagonal")
+        Kt = torch.from_numpy(np.ascontiguousarray(Kh)).to(dev)
+    if tuple(Kt.shape) == (3, 3):
+        Kt = Kt.reshape(1, 9).expand(nimg, 9)
+    elif tuple(Kt.shape) not in ((nimg, 3, 3), (nimg, 9)):   # ([nimg, 9]: this function's own result)
+        raise ValueError(f"{who}: K must be [3, 3] or [{nimg}, 3, 3]")
+    return Kt.reshape(nimg, 9).contiguous()
+
+
+def _tracks_ctx(tracks):
+    import torch
+    from . import _abi
+    from ._native import context_for
+    dev = tracks.xy.device
+    return context_for(_abi.params_from_dict({}, _abi.SFM_MODE_NAIVE), dev.index or 0), dev, \
+        torch.cuda.current_stream(dev).cuda_stream
+
+
+def resect_frames(tracks, X, K, posed=None, iterations=None, threshold: float = PNP_THRESHOLD, min_inliers: int = 12,
+                  seed: int = 5) -> Resected:
+    """The pose of every frame without one from the 2D-3D links its tracks give it, all frames in
+    one call on the device (include/sfmfeat.h sfm_resect_tracks_dev has the rule in full): row r of
+    slot s is linked to X[tracks.node_track[s][r]]; a 6-point RANSAC per slot over those links
+    (reprojection error < `threshold` pixels), the winner refined on its inliers.
+
+    tracks: build_tracks' result.  X [n_tracks, 3]: triangulate_tracks' points (numpy, uploaded, or a
+    device tensor, used in place; NaN = no point).  K: [3, 3], or [nimg, 3, 3] with one matrix per
+    slot; a host K must be finite and upper triangular with a non-zero diagonal (ValueError), a
+    device K is used in place and a slot whose K is not is left unattempted.  posed (optional)
+    [nimg]: the slots to skip.  iterations=None is pose.calculate_num_ransac_iterations(0.98, 6, 0.5)
+    = 248.  threshold defaults to pose.PNP_THRESHOLD, 8 px.  min_inliers=12, twice the sample size,
+    is how verify_matches chose its 16.  Samples depend on (seed, the slot, the sample's number) only.
+    Enqueued on torch's current stream; nothing synchronises until a host property of the result is
+    read."""
+    import torch
+    from . import pose
+    ctx, dev, stream = _tracks_ctx(tracks)
+    nimg, cap = int(tracks.xy.shape[0]), int(tracks.xy.shape[1])
+    iters = pose.calculate_num_ransac_iterations(0.98, 6, 0.5) if iterations is None else int(iterations)
+    thr = float(threshold)
+    with torch.cuda.device(dev):
+        Kt = _slot_K(torch, K, nimg, dev, "resect_frames")
+        Xt = X if isinstance(X, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(X, np.float64)))
+        if Xt.dim() != 2 or Xt.shape[1] != 3:
+            raise ValueError("resect_frames: X must be [n_tracks, 3]")
+        Xt = Xt.to(device=dev, dtype=torch.float64).contiguous()
+        T = int(Xt.shape[0])
+        count = getattr(tracks, "count_dev", None)
+        if count is None:
+            count = torch.full((nimg,), cap, dtype=torch.int32, device=dev)
+        attempt = None
+        if posed is not None:
+            pm = posed if isinstance(posed, torch.Tensor) else torch.from_numpy(np.asarray(posed))
+            if pm.numel() != nimg:
+                raise ValueError("resect_frames: posed must have one entry per slot")
+            attempt = (pm.reshape(-1).to(dev) == 0).to(torch.uint8).contiguous()
+        rt = torch.empty((nimg, 12), dtype=torch.float64, device=dev)
+        rstat = torch.empty((nimg, 8), dtype=torch.int32, device=dev)
+        rcost = torch.empty((nimg, 2), dtype=torch.float64, device=dev)
+        rkeep = torch.empty((nimg, cap), dtype=torch.uint8, device=dev)
+        ctx.resect_tracks_dev(tracks.xy, count, tracks.node_track_dev, Xt if T else None, T, Kt, attempt, iters, thr,
+                              int(min_inliers), int(seed), pose.REFINE_MAX_ITER, rt, rstat, rcost, rkeep, None, None,
+                              stream)
+    return Resected(rt, rstat, rcost, rkeep, Kt)
+
+
+class Reconstruction:
+    """What `reconstruct` leaves: `P_dev` [nimg, 12] and `X_dev` [n_tracks, 3] float64 on the device;
+    on the host `P` [nimg, 3, 4], `R` [nimg, 3, 3], `t` [nimg, 3] (NaN for a slot without a pose),
+    `posed` [nimg] bool, `X` [n_tracks, 3] (NaN: fewer than two posed views), `views` [n_tracks] and
+    `rounds`, the slots that joined in each round (the seed pair first)."""
+
+    def __init__(self, tracks, K, R, t, posed, P_dev, X_dev, views_dev, rounds):
+        self.tracks, self.K, self.R, self.t, self.posed = tracks, K, R, t, posed
+        self.P_dev, self.X_dev, self._views_dev, self.rounds = P_dev, X_dev, views_dev, rounds
+        self._host = {}
+
+    @property
+    def P(self) -> np.ndarray:
+        return self.K @ np.concatenate([self.R, self.t[:, :, None]], axis=2)
+
+    @property
+    def X(self) -> np.ndarray:
+        if "X" not in self._host:
+            self._host["X"] = self.X_dev.cpu().numpy()
+        return self._host["X"]
+
+    @property
+    def views(self) -> np.ndarray:
+        if "views" not in self._host:
+            self._host["views"] = self._views_dev.cpu().numpy()
+        return self._host["views"]
+
+    def ba_inputs(self):
+        """(camera_indices, point_indices, points_2d, camera_params [nimg, 6], points_3d) for
+        pose.BundleAdjustment(nimg, len(points_3d), ..., K_list): the observations of posed slots on
+        tracks with a point, the points re-indexed to those tracks in order, a camera's index its
+        slot.  camera_params holds (Rodrigues vector, t) and zeros for a slot without a pose, which
+        no observation refers to."""
+        from . import pose
+        cam, pt, xy = self.tracks.ba_inputs()
+        good = np.isfinite(self.X).all(axis=1)
+        sel = good[pt] & self.posed[cam]
+        remap = np.cumsum(good) - 1
+        params = np.zeros((len(self.posed), 6))
+        for s in np.flatnonzero(self.posed):
+            params[s, :3] = pose.rodrigues(self.R[s])[0].reshape(3)
+            params[s, 3:] = self.t[s]
+        return cam[sel], remap[pt[sel]], xy[sel], params, self.X[good]
+
+
+def reconstruct(tracks, K, seed_pair, per_round=None, max_rounds=None, **resect_kwargs) -> Reconstruction:
+    """From the initial pair to a pose for every frame the tracks can give one, on the device.
+    seed_pair: (a, b, R, t) as `TwoView.seed` returns it.  P[a] = K_a [I | 0] and P[b] = K_b [R | t];
+    all tracks are triangulated from the posed slots (pose.triangulate_tracks); then, round after
+    round, `resect_frames` runs over the slots without a pose, those it poses are accepted in
+    `next_views()` order (per_round=None: all of them, an int: that many), their P is set and all
+    tracks are triangulated again.  The loop ends with the round that accepts nothing (or after
+    max_rounds rounds).  K and **resect_kwargs as resect_frames takes them.
+
+    One small host read per round (the resection's rstat [nimg, 8], to decide which slots join) is
+    the only read-back, and the indices of the slots that join (a few int64) are the only upload;
+    the points, the tracks, the poses and the mask of posed slots stay on the device.
+    Out of scope: bundle adjustment inside the loop, filtering tracks by
+    reprojection error, re-resection of posed frames."""
+    import torch
+    from . import pose
+    a, b, R01, t01 = seed_pair
+    ctx, dev, stream = _tracks_ctx(tracks)
+    nimg = int(tracks.xy.shape[0])
+    a, b = int(a), int(b)
+    if not (0 <= a < nimg and 0 <= b < nimg) or a == b:
+        raise ValueError("reconstruct: the seed pair's slots must be two different slots of the table")
+    with torch.cuda.device(dev):
+        Kt = _slot_K(torch, K, nimg, dev, "reconstruct")
+        K3 = Kt.reshape(nimg, 3, 3)
+        rt = torch.full((nimg, 12), float("nan"), dtype=torch.float64, device=dev)
+        P = torch.zeros((nimg, 12), dtype=torch.float64, device=dev)
+        valid = torch.zeros(nimg, dtype=torch.uint8, device=dev)
+        posed = np.zeros(nimg, bool)
+
+        def set_pose(slots, source):   # rt, P and valid of `slots` from source(idx) [len(slots), 12], on the device
+            idx = torch.from_numpy(np.asarray(slots, np.int64)).to(dev)   # (the round's one upload)
+            src = source(idx)
+            rt[idx] = src
+            Rt34 = torch.cat([src[:, :9].reshape(-1, 3, 3), src[:, 9:].reshape(-1, 3, 1)], dim=2)
+            P[idx] = torch.bmm(K3[idx], Rt34).reshape(-1, 12)
+            valid[idx] = 1
+            posed[slots] = True
+
+        first = np.concatenate([np.eye(3).reshape(9), np.zeros(3), np.asarray(R01, np.float64).reshape(9),
+                                np.asarray(t01, np.float64).reshape(3)]).reshape(2, 12)
+        first = torch.from_numpy(first).to(dev)
+        set_pose([a, b], lambda idx: first)
+        rounds = [[a, b]]
+        X, views = pose.triangulate_tracks(tracks, P, valid)
+        while max_rounds is None or len(rounds) - 1 < int(max_rounds):
+            res = resect_frames(tracks, X, Kt, posed=valid, **resect_kwargs)   # (valid: the posed mask, resident)
+            order = res.next_views()          # (the round's one host read: rstat)
+            if per_round is not None:
+                order = order[:max(int(per_round), 0)]
+            joined = [int(s) for s in order]
+            rounds.append(joined)
+            if not joined:
+                break
+            set_pose(joined, lambda idx: res.pose_dev[idx])
+            X, views = pose.triangulate_tracks(tracks, P, valid)
+        Kh = K3.cpu().numpy()
+        rth = rt.cpu().numpy()
+        R, t = rth[:, :9].reshape(nimg, 3, 3), rth[:, 9:]
+    return Reconstruction(tracks, Kh, R, t, posed, P, X, views, rounds)
